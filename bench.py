@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- aligned reads/s of the MI355X hot path on BASELINE.json's metric.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times exactly K steps, writes the last step's results under DIR when --dump-outputs is given (dump_outputs below), and
+prints the headline line.  Everything else it can measure (the median of several blocks, the roofline, the D2H / post-filter rates, the other read
+lengths, the command line end to end, the host ceiling, the CPU baseline and the comparison with the reference) runs with --full only.
 
 Workload (config.workload): hg18 is not available anywhere, so the run uses this repo's seeded
 hg18-like synthetic genome (tools/yaha_sim.cpp: 41 % GC, 45 % of bases in diverged Alu-/L1-like repeat families,
@@ -16,7 +20,7 @@ context's latency-bound stages overlap the other's compute (contexts share nothi
 reads per GPU), the index is replicated per GPU, there is no data-path collective: torch.distributed is used
 for the barrier and the max-over-ranks only.
 
-Adds to the JSON line:  "roofline" for the dominant kernel (k_ext_rows: the X-drop extension rows) from HIP events
+--full adds to the JSON line:  "roofline" for the dominant kernel (k_ext_rows: the X-drop extension rows) from HIP events
 on the stream it is launched on, and "cpu_baseline": the real reference binary (oracle/_ref/yaha -t <cores>) -- or,
 where that is absent, the oracle port -- timed on a bounded sample of the same reads on this box's host cores.
 """
@@ -383,8 +387,9 @@ def make_room(cache, need_gb=40.0):
         sys.stderr.write("[bench] make_room: %s\n" % e)
 
 
-def run_contexts(ctxs, steps, collect=False, postfilter=False):
-    """`steps` passes of the hot path shared out to the contexts (one host thread each, a common counter); returns (seconds, summed stage ms)."""
+def run_contexts(ctxs, steps, collect=False, postfilter=False, last=None):
+    """`steps` passes of the hot path shared out to the contexts (one host thread each, a common counter); returns (seconds, summed stage ms).
+    `last` (a list): the context that took the last step is appended to it."""
     import threading
     stage_ms, lock, todo, flt, flt_err = {}, threading.Lock(), [steps], {}, []
 
@@ -394,6 +399,8 @@ def run_contexts(ctxs, steps, collect=False, postfilter=False):
                 if todo[0] <= 0:
                     return
                 todo[0] -= 1
+                if todo[0] == 0 and last is not None:
+                    last.append(c)
             c.run()                                     # synchronous: returns when the results are complete in HBM
             if postfilter:
                 # OQC / FBS / MAPQ on the device (oqc_stage.h) and D2H of the clumps that are printed -- on a thread of its own, on the stage's snapshot of the
@@ -527,6 +534,49 @@ def end_to_end(ya, idx, fa, cache, n_reads, seed, gpus=1, read_len=1000, div=0.0
             "read_len": read_len, "command": "yaha -x IDX -q %d_reads.fa -osh /dev/shm/out.sam%s (defaults: -ctx 3, batches of ~16 M bases, host threads from the usable CPUs)" % (n_reads, " -gpus %d" % gpus if gpus > 1 else "")}
 
 
+def dump_outputs(r, out_dir, max_bytes=64 << 20, max_sample_reads=2048, seed=4242):
+    """What a caller of the hot path receives for the last timed step (the ResultBatch of ygpu_collect), as .npy files in float64 / float32, at most
+    `max_bytes` in all, so that two builds can be compared output for output on the same inputs:
+      counters.npy      float64 [16]            the batch's counters (yaha_amd.COUNTER_NAMES order)
+      clump_start.npy   float64 [n_reads + 1]   every read's first clump (the whole batch)
+      sample_reads.npy  float64 [m]             a fixed, seeded sample of the reads (ascending), cut where the bytes below would pass the limit
+      clumps.npy        float64 [k, 11]         the sampled reads' clumps in order: CLUMP_FIELDS (op_start is left out: it locates the ops, ops.npy holds them)
+      ops.npy           float32 [l]             their edit ops in the same order, len | op character << 16 (16 + 8 bits, as result_records reads them: exact in float32)
+    Under --gpus N > 1 these are rank 0's results, for its shard of the reads."""
+    import numpy as np
+    CLUMP_FIELDS = ("sro", "sqo", "eqo", "refLen", "totScore", "totLength", "matchedBases", "mismatchedBases", "gapBases", "status", "n_ops")
+
+    def view(ptr, n, dtype):
+        dtype = np.dtype(dtype)
+        if n == 0:
+            return np.zeros(0, dtype)
+        return np.frombuffer((C.c_char * (n * dtype.itemsize)).from_address(C.cast(ptr, C.c_void_p).value), dtype=dtype)
+
+    def ranges(starts, lens):                    # the indices start[i] .. start[i] + len[i] - 1, one range after the other
+        lens = lens.astype(np.int64)
+        return np.repeat(starts.astype(np.int64) - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()), dtype=np.int64)
+    import yaha_amd as ya
+    n_reads = int(r.n_reads)
+    cs = view(r.clump_start, n_reads + 1, np.uint32).astype(np.int64)
+    clumps = view(r.clumps, int(r.n_clumps), ya.Clump)
+    ops = view(r.ops, int(r.n_ops), np.uint32)
+    ops_before = np.concatenate([[0], np.cumsum(clumps["n_ops"], dtype=np.int64)])          # edit ops of the clumps before clump i
+    order = np.random.default_rng(seed).permutation(n_reads)[:max_sample_reads]
+    budget = max_bytes - 8 * (n_reads + 1) - 8 * len(order) - (64 << 10)                     # (64 KB for the counters and the five .npy headers)
+    read_bytes = 8 * len(CLUMP_FIELDS) * (cs[order + 1] - cs[order]) + 4 * (ops_before[cs[order + 1]] - ops_before[cs[order]])
+    sample = np.sort(order[:int(np.searchsorted(np.cumsum(read_bytes), budget, side="right"))])
+    sel = clumps[ranges(cs[sample], cs[sample + 1] - cs[sample])]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "counters.npy"), np.array([getattr(r.counters, k) for k in ya.COUNTER_NAMES], dtype=np.float64))
+    np.save(os.path.join(out_dir, "clump_start.npy"), cs.astype(np.float64))
+    np.save(os.path.join(out_dir, "sample_reads.npy"), sample.astype(np.float64))
+    np.save(os.path.join(out_dir, "clumps.npy"), np.stack([sel[f].astype(np.float64) for f in CLUMP_FIELDS], axis=1).reshape(len(sel), len(CLUMP_FIELDS)))
+    op_idx = ranges(sel["op_start"], sel["n_ops"])
+    op = ops[op_idx]
+    np.save(os.path.join(out_dir, "ops.npy"), ((op & 0xFFFF) | (((op >> 16) & 0xFF) << 16)).astype(np.float32))
+    log("outputs of the last step in %s: %d of %d reads sampled, %d clumps, %d ops" % (out_dir, len(sample), n_reads, len(sel), len(op_idx)))
+
+
 def stub_rank(args, rank, world):
     """YAHA_BENCH_STUB=1 (tests only, CPU tier): the launch / rendezvous / barrier / max-over-ranks / one-JSON-line plumbing of the N > 1 path with a
     sleep in place of the device step -- no GPU, gloo instead of RCCL.  Never a measurement: the line says so."""
@@ -574,7 +624,23 @@ def launch_ranks(n, argv):
         raise SystemExit(rc if rc != 0 else 1)
 
 
-def main():
+def bench_cache():
+    return os.environ.get("YAHA_BENCH_CACHE", "/tmp/yaha_bench_cache")
+
+
+def prepare_inputs():
+    """The seeded inputs of a plain run with the default arguments -- genome, index and the reads of rank 0 -- generated ahead of it (__graft_entry__.build()
+    calls this where a GPU is present: the 3.1 Gbp genome and its index take ~30 s, which a run would otherwise spend before its first step)."""
+    args = arg_parser().parse_args([])
+    cache = bench_cache()
+    make_room(cache)
+    mbp = pick_genome_mbp(cache, args.seed)
+    fa, _idx = ensure_inputs(cache, mbp, args.seed)
+    make_reads(cache, fa, "g%dm" % mbp, args.reads_per_gpu, args.read_len, args.div, 1000)
+    log("inputs of a plain run ready in %s (%d Mbp genome)" % (cache, mbp))
+
+
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -584,14 +650,25 @@ def main():
     ap.add_argument("--genome-mbp", type=int, default=0, help="synthetic genome size; 0 = G-hg18scale (3 100 Mbp: the index the metric is quoted on) when the box has the disk and memory for it, else 100")
     ap.add_argument("--div", type=float, default=0.017)
     ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--cpu-seconds", type=float, default=60.0, help="CPU-baseline budget (wall seconds of the reference over all its thread counts)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick-extras", action="store_true", help="of the legs after the timed region only the D2H- and post-filter-inclusive rates (for A/Bs of the filter stage)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the legs measured after the timed region (other read lengths, D2H-inclusive rate, command line)")
-    ap.add_argument("--e2e-reads", type=int, default=1048576, help="reads of the end-to-end command-line leg (BASELINE config 4: 1 M x 1 kbp)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the median of --blocks blocks, the roofline, and the legs after the timed region "
+                    "(D2H / post-filter rates, other read lengths, command line, host ceiling, CPU baseline, comparison with the reference)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the results of the last timed step to DIR/*.npy (dump_outputs); with --gpus N > 1, rank 0's shard of the reads")
+    ap.add_argument("--cpu-seconds", type=float, default=60.0, help="with --full: CPU-baseline budget (wall seconds of the reference over all its thread counts)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--quick-extras", action="store_true", help="with --full: of the legs after the timed region only the D2H- and post-filter-inclusive rates (for A/Bs of the filter stage)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the legs measured after the timed region (other read lengths, D2H-inclusive rate, command line)")
+    ap.add_argument("--e2e-reads", type=int, default=1048576, help="with --full: reads of the end-to-end command-line leg (BASELINE config 4: 1 M x 1 kbp)")
     ap.add_argument("--contexts", type=int, default=4, help="device contexts (batches in flight) per GPU")
-    ap.add_argument("--blocks", type=int, default=5, help="the timed region is this many back-to-back blocks of --steps steps; the median block is the headline")
-    args = ap.parse_args()
+    ap.add_argument("--blocks", type=int, default=None, help="the timed region is this many back-to-back blocks of --steps steps; the median block is the headline "
+                    "(default 1, with --full 5)")
+    return ap
+
+
+def main():
+    args = arg_parser().parse_args()
+    t_start = time.time()
+    if args.blocks is None:
+        args.blocks = 5 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, sys.argv[1:])       # nothing above has imported torch or touched a GPU
@@ -623,7 +700,7 @@ def main():
         torch.cuda.synchronize()
 
     import yaha_amd as ya
-    cache = os.environ.get("YAHA_BENCH_CACHE", "/tmp/yaha_bench_cache")
+    cache = bench_cache()
     if rank == 0:
         make_room(cache)
         if args.genome_mbp <= 0:
@@ -634,6 +711,7 @@ def main():
         args.genome_mbp = pick_genome_mbp(cache, args.seed)              # rank 0 has built it by now: the same answer on every rank
     fa, idx = ensure_inputs(cache, args.genome_mbp, args.seed)
     reads_path = make_reads(cache, fa, "g%dm" % args.genome_mbp, args.reads_per_gpu, args.read_len, args.div, 1000 + rank)
+    t_inputs = time.time()
 
     with ya.Session(["-x", idx, "-q", reads_path]) as s:
         b = s.next_batch(args.reads_per_gpu)
@@ -662,45 +740,51 @@ def main():
                 break
         t_up /= len(ctxs)
         args.contexts = len(ctxs)
+        t_ctx = time.time()
         for c in ctxs:
             for _ in range(args.warmup):
                 c.run()
-        # The timed region: args.blocks back-to-back blocks of EXACTLY args.steps steps, each bracketed by barrier + synchronize on both sides.  The headline is the
-        # MEDIAN block (a 0.9 s block cannot resolve a 1 % kernel change against the box's run-to-run spread; five of them and their min / max can).
-        block_dt, stage_ms = [], {}
+        log("set-up %.1f s: torch and inputs %.1f, %d contexts up %.1f, warm-up %.1f" % (time.time() - t_start, t_inputs - t_start, len(ctxs), t_ctx - t_inputs, time.time() - t_ctx))
+        # The timed region: args.blocks back-to-back blocks of EXACTLY args.steps steps (one block unless --full or --blocks asks for more), each bracketed by
+        # barrier + synchronize on both sides.  The headline is the MEDIAN block (with --full: a 0.9 s block cannot resolve a 1 % kernel change against the box's
+        # run-to-run spread; five of them and their min / max can).
+        block_dt, stage_ms, last = [], {}, []
         for _b in range(max(1, args.blocks)):
             barrier()
             t0 = time.time()
-            _dt_inner, st_b = run_contexts(ctxs, args.steps)
+            _dt_inner, st_b = run_contexts(ctxs, args.steps, last=last)
             barrier()
             block_dt.append(time.time() - t0)
             for k2, v in st_b.items():
                 stage_ms[k2] = stage_ms.get(k2, 0.0) + v / max(1, args.blocks)      # mean over the blocks of the per-block sums
         # ---- after the timed region ----
-        t = time.time(); r = ctxs[0].collect(); t_down = time.time() - t
-        try:
-            tv = ctxs[0].trace_volume()          # the trace stream of the batch's last run: records written against records a traceback can visit
-        except Exception as e:
-            tv = None; log("trace volume: %s" % str(e)[:200])
-        counters = r.counters.as_dict()
-        n_clumps = int(r.n_clumps); n_ops = int(r.n_ops)
-        d2h = None; unshared_rows_ms = None
-        if world == 1 and not args.no_extras:
-            # the dominant kernel with the chip to itself: two steps of one context (in the timed region the launches of the contexts share the CUs, and a launch's
-            # duration -- first wave's start to last wave's end -- stretches by whatever the others' kernels take from it)
-            _dt1, st1 = run_contexts(ctxs[:1], 2)
-            unshared_rows_ms = st1.get("ext_rows_device_clock", 0.0) / 2 or None
-            dt2, _st = run_contexts(ctxs, args.steps, collect=True)     # every step also copies its results to host memory (the other context computes meanwhile)
-            d2h = {"value_with_d2h": n_reads * args.steps / dt2, "ms_per_step": 1e3 * dt2 / args.steps, "result_bytes_per_step": 32 * n_clumps + 4 * n_ops + 4 * (n_reads + 1)}
-            # ... and with the post-filter on the device instead (what the command line does): every step = hot path + OQC/FBS/MAPQ of all reads + D2H of the printed clumps only
+        if args.dump_outputs and rank == 0:
+            dump_outputs(last[-1].collect(), args.dump_outputs)      # the context that took the last timed step (every context runs the same batch)
+        if args.full:
+            t = time.time(); r = ctxs[0].collect(); t_down = time.time() - t
             try:
-                for c in ctxs:
-                    c.set_postfilter(s)
-                f = ctxs[0].postfilter(); fb = 40 * int(f.n_clumps) + 4 * int(f.n_ops) + 4 * (n_reads + 1)
-                dt3, _st3 = run_contexts(ctxs, args.steps, postfilter=True)
-                d2h.update({"value_with_postfilter": n_reads * args.steps / dt3, "ms_per_step_with_postfilter": 1e3 * dt3 / args.steps, "filtered_result_bytes_per_step": fb, "printed_clumps_per_read": int(f.n_clumps) / n_reads})
+                tv = ctxs[0].trace_volume()          # the trace stream of the batch's last run: records written against records a traceback can visit
             except Exception as e:
-                d2h["postfilter_error"] = str(e)[:200]
+                tv = None; log("trace volume: %s" % str(e)[:200])
+            counters = r.counters.as_dict()
+            n_clumps = int(r.n_clumps); n_ops = int(r.n_ops)
+            d2h = None; unshared_rows_ms = None
+            if world == 1 and not args.no_extras:
+                # the dominant kernel with the chip to itself: two steps of one context (in the timed region the launches of the contexts share the CUs, and a launch's
+                # duration -- first wave's start to last wave's end -- stretches by whatever the others' kernels take from it)
+                _dt1, st1 = run_contexts(ctxs[:1], 2)
+                unshared_rows_ms = st1.get("ext_rows_device_clock", 0.0) / 2 or None
+                dt2, _st = run_contexts(ctxs, args.steps, collect=True)     # every step also copies its results to host memory (the other context computes meanwhile)
+                d2h = {"value_with_d2h": n_reads * args.steps / dt2, "ms_per_step": 1e3 * dt2 / args.steps, "result_bytes_per_step": 32 * n_clumps + 4 * n_ops + 4 * (n_reads + 1)}
+                # ... and with the post-filter on the device instead (what the command line does): every step = hot path + OQC/FBS/MAPQ of all reads + D2H of the printed clumps only
+                try:
+                    for c in ctxs:
+                        c.set_postfilter(s)
+                    f = ctxs[0].postfilter(); fb = 40 * int(f.n_clumps) + 4 * int(f.n_ops) + 4 * (n_reads + 1)
+                    dt3, _st3 = run_contexts(ctxs, args.steps, postfilter=True)
+                    d2h.update({"value_with_postfilter": n_reads * args.steps / dt3, "ms_per_step_with_postfilter": 1e3 * dt3 / args.steps, "filtered_result_bytes_per_step": fb, "printed_clumps_per_read": int(f.n_clumps) / n_reads})
+                except Exception as e:
+                    d2h["postfilter_error"] = str(e)[:200]
         k = s.params.wordLen
         for c in reversed(ctxs):
             c.close()
@@ -719,47 +803,9 @@ def main():
     steps = args.steps
     total_reads = world * n_reads * steps
     value = total_reads / dt
-    # ALGORITHMIC bytes per read, SURVEY.md 8(d): read codes + 2 strands x 2 u32 table words per k-mer + hit words + touched reference nibbles
-    # (lazy: rows computed + band per call + exact-match bases) + result records; H, R and the records are counted on the device for this input.
     Lq = n_bases / n_reads
-    B = Lq + 16 * (Lq - k + 1) + 4 * counters["hits"] / n_reads + counters["ref_bases_touched"] / n_reads / 2 + (24 * counters["clumps_scored"] + 3 * counters["ops_out"]) / n_reads
-    # Dominant kernel (profiles/): k_ext_rows, the X-drop extension rows of all reads of the batch, one problem per lane.  One launch processes the batch's
-    # n_reads reads, so its algorithmic bytes are B x n_reads (SURVEY 8(d)'s per-read figure x the reads of one launch).  Duration: measured live in the
-    # timed region -- HIP events around the launch on its stream (`ext_rows`) and the kernel's own wall_clock64() stamps (`ext_rows_device_clock`); with
-    # several contexts per GPU the event bracket also contains the time the launch queues behind the other context's kernels, so the device-clock duration
-    # (which is what rocprofv3 reports for the kernel, profiles/) is the one used.
-    align_ms = stage_ms.get("align_dp", 0.0) / steps
     rows_ms = stage_ms.get("ext_rows", 0.0) / steps
-    rows_dev_ms = stage_ms.get("ext_rows_device_clock", 0.0) / steps
-    if rows_ms > 0:
-        packed = stage_ms.get("ext_rows_packed16", 0.0) > 0       # a flag among the timings: the packed 16-bit kernel ran (16-byte trace records instead of 12-byte rows)
-        kname, kernel_ms = "k_ext_rows", (rows_dev_ms if rows_dev_ms > 0 else rows_ms)
-        stream_bytes = (17.0 if packed else 13.5) * counters["dp_ext_rows"] + 48.0 * counters["dp_ext_calls"]     # what the kernel itself streams: per row a query code (1/2 B packed in the 16-bit kernel, 1 B in the 32-bit one) + 1/2 B reference + 16 (12) B of trace cells; 48 B per problem
-    else:                                                    # other band widths run the wave-per-root kernel
-        packed = False
-        kname, kernel_ms, stream_bytes = "k_align", align_ms, None
-    kbytes = B * n_reads
-    achieved = (kbytes / (kernel_ms * 1e-3)) / 1e9 if kernel_ms > 0 else 0.0
-    ach_un = (kbytes / (unshared_rows_ms * 1e-3)) / 1e9 if (rows_ms > 0 and unshared_rows_ms) else None      # the same launch with the chip to itself
-    # HBM traffic of that launch from the PMC counters: bench.py cannot read hardware counters of its own process, so this is the figure of the last
-    # profiling pass of the same command (tools/pmc_pass.sh -> profiles/pmc_latest.json), used only when it was taken on the same batch size and kernel.
-    traffic, pmc = None, None
-    pj = os.path.join(ROOT, "profiles", "pmc_latest.json")
-    if os.path.exists(pj):
-        try:
-            pmc = json.load(open(pj))
-            import hashlib
-            dev = os.path.join(ROOT, "yaha_amd", "csrc", "device")
-            ksrc = hashlib.sha256(b"".join(open(os.path.join(dev, f), "rb").read() for f in ("ext_lanes.h", "ext_lanes_pk.h"))).hexdigest()[:16]
-            # counters of another kernel are worse than none: the file names the sources of the extension kernels it was measured on (tools/pmc_summary.py)
-            if pmc.get("reads_per_gpu") == n_reads and pmc.get("kernel") == kname and pmc.get("kernel_source_sha16") == ksrc:
-                traffic = pmc.get("hbm_bytes_per_launch")
-            else:
-                pmc = None
-        except Exception:
-            traffic, pmc = None, None
-    valu = pmc.get("valu_insts_per_launch") if pmc else None
-    simd_cycles = 1024 * 2.4e9 * (unshared_rows_ms if (rows_ms > 0 and unshared_rows_ms) else kernel_ms) * 1e-3   # 256 CUs x 4 SIMDs at 2.4 GHz over the launch (the counters are a one-context profile's: priced against the unshared duration when it was measured)
+    packed = rows_ms > 0 and stage_ms.get("ext_rows_packed16", 0.0) > 0      # a flag among the timings: the packed 16-bit kernel ran (16-byte trace records instead of 12-byte rows)
     out = {
         "metric": "aligned reads/s (whole node), 1 000 bp reads, OQC mode hot path", "value": value, "unit": "reads/s",
         "n_gpus": world, "ranks_seen": ranks_seen, "steps": steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / steps, "ms_per_step_min": 1e3 * min(block_dt) / steps, "ms_per_step_max": 1e3 * max(block_dt) / steps, "blocks": len(block_dt), "ms_per_step_blocks": [round(1e3 * x / steps, 3) for x in block_dt],
@@ -773,103 +819,143 @@ def main():
                    % (args.genome_mbp, n_reads, args.read_len, 100 * args.div),
                    "genome_mbp": args.genome_mbp, "contexts_per_gpu": max(1, args.contexts), "options": "-BW 5 -G 50 -H 650 -M 25 -X 25 -L 15",
                    "reads_per_gpu": n_reads, "read_len": args.read_len, "parallelism": "reads sharded x%d, index replicated, no collective; %d contexts (batches in flight) per GPU" % (world, max(1, args.contexts))},
-        "roofline": {"bound": "hbm", "kernel": kname, "unshared": ({"kernel_ms_per_launch": unshared_rows_ms, "achieved": kbytes / (unshared_rows_ms * 1e-3) / 1e9, "frac": kbytes / (unshared_rows_ms * 1e-3) / 8.0e12,
-                                                                   "note": "the same launch with one context on the GPU (two steps after the timed region): what rocprofv3 reports for the kernel in profiles/*_one_context.csv"} if (rows_ms > 0 and unshared_rows_ms) else None), "kernel_variant": ("k_ext_rows_pk (packed 16-bit, two cells per instruction)" if (rows_ms > 0 and packed) else ("k_ext_rows (32-bit)" if rows_ms > 0 else kname)), "achieved": (ach_un if ach_un else achieved), "peak": 8000.0, "unit": "GB/s", "frac": (ach_un if ach_un else achieved) / 8000.0, "traffic": traffic,
-                     "frac_basis": ("one context on the GPU (full-chip launch), measured in this run after the timed region: what profiles/*_one_context.csv reproduces" if ach_un else "in the timed region"),
-                     "frac_unshared": (ach_un / 8000.0 if ach_un else None), "kernel_ms_unshared": unshared_rows_ms, "achieved_in_run": achieved, "frac_in_run": achieved / 8000.0, "kernel_ms_in_run": kernel_ms,
-                     "trace_bytes_useful_frac": (tv["records_visitable"] / tv["records_written"] if (tv and tv["records_written"]) else None),
-                     "trace_bytes_written": (tv["records_written"] * tv["record_bytes"] if tv else None), "trace_bytes_visitable": (tv["records_visitable"] * tv["record_bytes"] if tv else None),
-                     "trace_calls": (tv["calls"] if tv else None), "trace_calls_walking": (tv["walkers"] if tv else None), "whole_path_traffic": ((pmc or {}).get("whole_path") or {}).get("hbm_bytes_per_step"),
-                     "algorithmic_bytes_per_launch": kbytes, "algorithmic_bytes_per_read": B, "reads_per_launch": n_reads, "kernel_ms_per_launch": kernel_ms,
-                     "kernel_ms_hip_events": rows_ms, "kernel_ms_device_clock": rows_dev_ms,
-                     "kernel_stream_bytes_per_launch": stream_bytes, "kernel_stream_frac": (stream_bytes / (kernel_ms * 1e-3) / 8.0e12) if (stream_bytes and kernel_ms > 0) else None,
-                     "cell_updates_per_s": counters["dp_ext_cells"] / (kernel_ms * 1e-3) if kernel_ms > 0 else 0.0,
-                     "valu_frac_nominal": (valu * 2.0 / simd_cycles) if (valu and kernel_ms > 0) else None,
-                     "valu_frac_measured_mix": (valu * 4.0 / simd_cycles) if (valu and kernel_ms > 0) else None,
-                     "note": "a rows launch that shares the device with other batches takes 3/5 of the workgroups that fit and only one runs at a time (the others' latency-bound kernels run beside it): in the timed region it lasts longer BY DESIGN (`frac_in_run`, `kernel_ms_in_run`); `frac` / `achieved` are the same launch with the device to itself (`frac_unshared`, = the profiles' one-context figure) whenever that was measured; integer DP: `frac` follows SURVEY 8(d) (algorithmic bytes of the reads of one launch / kernel time / 8 TB/s) and is ~1% by construction; the kernel is bound by vector-ALU issue: valu_frac_nominal prices each wave64 VALU instruction at the nominal 2 SIMD cycles, valu_frac_measured_mix at what its mix measures: 4.4 cycles for the packed 16-bit kernel, 4.0 for the 32-bit one (DESIGN.md section 7); kernel_stream_frac counts the trace cells the kernel writes (an implementation choice, not algorithmic traffic)",
-                     "pmc": ({k2: pmc[k2] for k2 in ("valu_insts_per_launch", "fetch_bytes_per_launch", "write_bytes_per_launch", "lds_bank_conflict_frac", "gpu_busy_cycles", "git_head", "kernel_source_sha16", "source") if k2 in pmc} if pmc else None)},
-        "path": {"algorithmic_bytes_per_read": B, "hbm_frac_whole_path": value * B / (8.0e12 * world),
-                 "dp_cell_updates_per_s": (counters["dp_ext_cells"] + counters["dp_gap_cells"]) * steps * world / dt},
         "stage_ms_per_step": {k2: v / steps for k2, v in stage_ms.items()},
-        "per_read": {k2: counters[k2] / n_reads for k2 in ("hits", "fragments", "clumps_formed", "clumps_scored", "dp_ext_calls", "dp_ext_rows", "dp_ext_cells", "dp_gap_calls", "dp_gap_rows", "dp_gap_cells", "splits", "ops_out", "ref_bases_touched")},
-        "pcie": {"upload_s": t_up, "collect_s": t_down, "clumps": n_clumps},
     }
-    if d2h:
-        out["value_with_d2h"] = d2h["value_with_d2h"]; out["d2h"] = d2h
-        if "value_with_postfilter" in d2h:
-            out["value_with_postfilter"] = d2h["value_with_postfilter"]
-    if world == 1 and not args.no_extras and not args.quick_extras:
-        # the same step on BASELINE's other read lengths (configs 1 and 3), and the whole command line (config 2 end to end)
-        wl = []
-        for label, n, length, div, nsteps in (("c1: 100 bp reads, r=0.02 (realised 0.7%)", 65536, 100, 0.007, 4), ("c3: 10 kbp reads, r=0.10 (realised 3.4%)", 1024, 10000, 0.034, 3)):
+    if args.full:
+        # ALGORITHMIC bytes per read, SURVEY.md 8(d): read codes + 2 strands x 2 u32 table words per k-mer + hit words + touched reference nibbles
+        # (lazy: rows computed + band per call + exact-match bases) + result records; H, R and the records are counted on the device for this input.
+        B = Lq + 16 * (Lq - k + 1) + 4 * counters["hits"] / n_reads + counters["ref_bases_touched"] / n_reads / 2 + (24 * counters["clumps_scored"] + 3 * counters["ops_out"]) / n_reads
+        # Dominant kernel (profiles/): k_ext_rows, the X-drop extension rows of all reads of the batch, one problem per lane.  One launch processes the batch's
+        # n_reads reads, so its algorithmic bytes are B x n_reads (SURVEY 8(d)'s per-read figure x the reads of one launch).  Duration: measured live in the
+        # timed region -- HIP events around the launch on its stream (`ext_rows`) and the kernel's own wall_clock64() stamps (`ext_rows_device_clock`); with
+        # several contexts per GPU the event bracket also contains the time the launch queues behind the other context's kernels, so the device-clock duration
+        # (which is what rocprofv3 reports for the kernel, profiles/) is the one used.
+        align_ms = stage_ms.get("align_dp", 0.0) / steps
+        rows_dev_ms = stage_ms.get("ext_rows_device_clock", 0.0) / steps
+        if rows_ms > 0:
+            kname, kernel_ms = "k_ext_rows", (rows_dev_ms if rows_dev_ms > 0 else rows_ms)
+            stream_bytes = (17.0 if packed else 13.5) * counters["dp_ext_rows"] + 48.0 * counters["dp_ext_calls"]     # what the kernel itself streams: per row a query code (1/2 B packed in the 16-bit kernel, 1 B in the 32-bit one) + 1/2 B reference + 16 (12) B of trace cells; 48 B per problem
+        else:                                                    # other band widths run the wave-per-root kernel
+            kname, kernel_ms, stream_bytes = "k_align", align_ms, None
+        kbytes = B * n_reads
+        achieved = (kbytes / (kernel_ms * 1e-3)) / 1e9 if kernel_ms > 0 else 0.0
+        ach_un = (kbytes / (unshared_rows_ms * 1e-3)) / 1e9 if (rows_ms > 0 and unshared_rows_ms) else None      # the same launch with the chip to itself
+        # HBM traffic of that launch from the PMC counters: bench.py cannot read hardware counters of its own process, so this is the figure of the last
+        # profiling pass of the same command (tools/pmc_pass.sh -> profiles/pmc_latest.json), used only when it was taken on the same batch size and kernel.
+        traffic, pmc = None, None
+        pj = os.path.join(ROOT, "profiles", "pmc_latest.json")
+        if os.path.exists(pj):
             try:
-                wl.append(side_workload(ya, idx, make_reads(cache, fa, "side", n, length, div, 2000), n, local, args.contexts, nsteps, label))
-            except Exception as e:
-                wl.append({"workload": label, "error": str(e)[:200]})
-        # the headline's int32 twin: the same batch with the X-drop extension rows in the 32-bit kernels (the reference computes in int; the packed 16-bit kernel is a
-        # lossless narrowing of the same recurrence, bit-identical results -- tests/test_gpu_parity.py::test_both_extension_kernel_families)
-        os.environ["YGPU_EXT32"] = "1"
-        try:
-            w32 = side_workload(ya, idx, reads_path, n_reads, local, args.contexts, max(3, steps // 2), "c2 with the 32-bit extension kernels (YGPU_EXT32=1), dtype int32", blocks=max(1, args.blocks))
-            w32["dtype"] = "int32"; wl.append(w32); out["value_int32"] = w32["reads_per_s"]; out["ms_per_step_int32"] = w32["ms_per_step"]; out["ms_per_step_int32_min_max"] = [w32["ms_per_step_min"], w32["ms_per_step_max"]]
-        except Exception as e:
-            wl.append({"workload": "c2 int32", "error": str(e)[:200]})
-        finally:
-            del os.environ["YGPU_EXT32"]
-        try:
-            wl.append(config5_leg(ya, idx, fa, cache, local, args.contexts, "g%dm" % args.genome_mbp))
-        except Exception as e:
-            wl.append({"workload": "c5", "error": str(e)[:300]})
-        wl.insert(1, {"workload": "c2: 1 kbp reads, r=0.05 (realised 1.7%) = the headline", "reads_per_step": n_reads, "steps": steps, "reads_per_s": value, "bases_per_s": value * Lq, "ms_per_step": 1e3 * dt / steps,
-                      "k_ext_rows_ms_per_step": rows_dev_ms})
-        out["workloads"] = wl
-        for w in wl:      # (flat copies: the driver's record drops nested lists)
-            tag = (w.get("workload") or "")[:2]
-            if tag in ("c1", "c3", "c5") and w.get("reads_per_s"):
-                out["value_" + tag] = w["reads_per_s"]
-                if w.get("verified") is not None: out["verified_" + tag] = bool(w["verified"].get("identical")) if isinstance(w["verified"], dict) else bool(w["verified"])
-        try:
-            out["end_to_end"] = end_to_end(ya, idx, fa, cache, args.e2e_reads, 3000)
-            out["e2e_reads_per_s"] = out["end_to_end"]["e2e_reads_per_s"]; out["steady_reads_per_s"] = out["end_to_end"]["steady_reads_per_s"]
-            out["contexts_up_ms"] = out["end_to_end"].get("contexts_up_ms")
-            if args.e2e_reads >= 262144:     # BASELINE config 3's shape through the command line as well: 32 768 reads of 10 kbp (20 batches of ~16 M bases), r = 0.10 (realised 3.4 %)
-                out["end_to_end_c3"] = end_to_end(ya, idx, fa, cache, 32768, 3100, read_len=10000, div=0.034, settle_s=40.0)
-                out["e2e_c3_reads_per_s"] = out["end_to_end_c3"].get("e2e_reads_per_s"); out["steady_c3_reads_per_s"] = out["end_to_end_c3"].get("steady_reads_per_s")
-        except Exception as e:
-            out["end_to_end"] = {"error": str(e)[:200]}
-        try:
-            out["host_ceiling"] = host_ceiling(ya, idx, os.path.join(cache, "e2e_n%d_l%d_s%d.fa" % (args.e2e_reads, 1000, 3000)))
-            out["host_ceiling_reads_per_s"] = out["host_ceiling"]["host_ceiling_reads_per_s"]
-        except Exception as e:
-            out["host_ceiling"] = {"error": str(e)[:300]}
-        if args.e2e_reads >= 262144:
+                pmc = json.load(open(pj))
+                import hashlib
+                dev = os.path.join(ROOT, "yaha_amd", "csrc", "device")
+                ksrc = hashlib.sha256(b"".join(open(os.path.join(dev, f), "rb").read() for f in ("ext_lanes.h", "ext_lanes_pk.h"))).hexdigest()[:16]
+                # counters of another kernel are worse than none: the file names the sources of the extension kernels it was measured on (tools/pmc_summary.py)
+                if pmc.get("reads_per_gpu") == n_reads and pmc.get("kernel") == kname and pmc.get("kernel_source_sha16") == ksrc:
+                    traffic = pmc.get("hbm_bytes_per_launch")
+                else:
+                    pmc = None
+            except Exception:
+                traffic, pmc = None, None
+        valu = pmc.get("valu_insts_per_launch") if pmc else None
+        simd_cycles = 1024 * 2.4e9 * (unshared_rows_ms if (rows_ms > 0 and unshared_rows_ms) else kernel_ms) * 1e-3   # 256 CUs x 4 SIMDs at 2.4 GHz over the launch (the counters are a one-context profile's: priced against the unshared duration when it was measured)
+        out.update({
+            "roofline": {"bound": "hbm", "kernel": kname, "unshared": ({"kernel_ms_per_launch": unshared_rows_ms, "achieved": kbytes / (unshared_rows_ms * 1e-3) / 1e9, "frac": kbytes / (unshared_rows_ms * 1e-3) / 8.0e12,
+                                                                       "note": "the same launch with one context on the GPU (two steps after the timed region): what rocprofv3 reports for the kernel in profiles/*_one_context.csv"} if (rows_ms > 0 and unshared_rows_ms) else None), "kernel_variant": ("k_ext_rows_pk (packed 16-bit, two cells per instruction)" if (rows_ms > 0 and packed) else ("k_ext_rows (32-bit)" if rows_ms > 0 else kname)), "achieved": (ach_un if ach_un else achieved), "peak": 8000.0, "unit": "GB/s", "frac": (ach_un if ach_un else achieved) / 8000.0, "traffic": traffic,
+                         "frac_basis": ("one context on the GPU (full-chip launch), measured in this run after the timed region: what profiles/*_one_context.csv reproduces" if ach_un else "in the timed region"),
+                         "frac_unshared": (ach_un / 8000.0 if ach_un else None), "kernel_ms_unshared": unshared_rows_ms, "achieved_in_run": achieved, "frac_in_run": achieved / 8000.0, "kernel_ms_in_run": kernel_ms,
+                         "trace_bytes_useful_frac": (tv["records_visitable"] / tv["records_written"] if (tv and tv["records_written"]) else None),
+                         "trace_bytes_written": (tv["records_written"] * tv["record_bytes"] if tv else None), "trace_bytes_visitable": (tv["records_visitable"] * tv["record_bytes"] if tv else None),
+                         "trace_calls": (tv["calls"] if tv else None), "trace_calls_walking": (tv["walkers"] if tv else None), "whole_path_traffic": ((pmc or {}).get("whole_path") or {}).get("hbm_bytes_per_step"),
+                         "algorithmic_bytes_per_launch": kbytes, "algorithmic_bytes_per_read": B, "reads_per_launch": n_reads, "kernel_ms_per_launch": kernel_ms,
+                         "kernel_ms_hip_events": rows_ms, "kernel_ms_device_clock": rows_dev_ms,
+                         "kernel_stream_bytes_per_launch": stream_bytes, "kernel_stream_frac": (stream_bytes / (kernel_ms * 1e-3) / 8.0e12) if (stream_bytes and kernel_ms > 0) else None,
+                         "cell_updates_per_s": counters["dp_ext_cells"] / (kernel_ms * 1e-3) if kernel_ms > 0 else 0.0,
+                         "valu_frac_nominal": (valu * 2.0 / simd_cycles) if (valu and kernel_ms > 0) else None,
+                         "valu_frac_measured_mix": (valu * 4.0 / simd_cycles) if (valu and kernel_ms > 0) else None,
+                         "note": "a rows launch that shares the device with other batches takes 3/5 of the workgroups that fit and only one runs at a time (the others' latency-bound kernels run beside it): in the timed region it lasts longer BY DESIGN (`frac_in_run`, `kernel_ms_in_run`); `frac` / `achieved` are the same launch with the device to itself (`frac_unshared`, = the profiles' one-context figure) whenever that was measured; integer DP: `frac` follows SURVEY 8(d) (algorithmic bytes of the reads of one launch / kernel time / 8 TB/s) and is ~1% by construction; the kernel is bound by vector-ALU issue: valu_frac_nominal prices each wave64 VALU instruction at the nominal 2 SIMD cycles, valu_frac_measured_mix at what its mix measures: 4.4 cycles for the packed 16-bit kernel, 4.0 for the 32-bit one (DESIGN.md section 7); kernel_stream_frac counts the trace cells the kernel writes (an implementation choice, not algorithmic traffic)",
+                         "pmc": ({k2: pmc[k2] for k2 in ("valu_insts_per_launch", "fetch_bytes_per_launch", "write_bytes_per_launch", "lds_bank_conflict_frac", "gpu_busy_cycles", "git_head", "kernel_source_sha16", "source") if k2 in pmc} if pmc else None)},
+            "path": {"algorithmic_bytes_per_read": B, "hbm_frac_whole_path": value * B / (8.0e12 * world),
+                     "dp_cell_updates_per_s": (counters["dp_ext_cells"] + counters["dp_gap_cells"]) * steps * world / dt},
+            "per_read": {k2: counters[k2] / n_reads for k2 in ("hits", "fragments", "clumps_formed", "clumps_scored", "dp_ext_calls", "dp_ext_rows", "dp_ext_cells", "dp_gap_calls", "dp_gap_rows", "dp_gap_cells", "splits", "ops_out", "ref_bases_touched")},
+            "pcie": {"upload_s": t_up, "collect_s": t_down, "clumps": n_clumps},
+        })
+        if d2h:
+            out["value_with_d2h"] = d2h["value_with_d2h"]; out["d2h"] = d2h
+            if "value_with_postfilter" in d2h:
+                out["value_with_postfilter"] = d2h["value_with_postfilter"]
+        if world == 1 and not args.no_extras and not args.quick_extras:
+            # the same step on BASELINE's other read lengths (configs 1 and 3), and the whole command line (config 2 end to end)
+            wl = []
+            for label, n, length, div, nsteps in (("c1: 100 bp reads, r=0.02 (realised 0.7%)", 65536, 100, 0.007, 4), ("c3: 10 kbp reads, r=0.10 (realised 3.4%)", 1024, 10000, 0.034, 3)):
+                try:
+                    wl.append(side_workload(ya, idx, make_reads(cache, fa, "side", n, length, div, 2000), n, local, args.contexts, nsteps, label))
+                except Exception as e:
+                    wl.append({"workload": label, "error": str(e)[:200]})
+            # the headline's int32 twin: the same batch with the X-drop extension rows in the 32-bit kernels (the reference computes in int; the packed 16-bit kernel is a
+            # lossless narrowing of the same recurrence, bit-identical results -- tests/test_gpu_parity.py::test_both_extension_kernel_families)
+            os.environ["YGPU_EXT32"] = "1"
             try:
-                out["eight_logical_devices"] = eight_logical_devices(ya, cache, args.seed, args.e2e_reads)
+                w32 = side_workload(ya, idx, reads_path, n_reads, local, args.contexts, max(3, steps // 2), "c2 with the 32-bit extension kernels (YGPU_EXT32=1), dtype int32", blocks=max(1, args.blocks))
+                w32["dtype"] = "int32"; wl.append(w32); out["value_int32"] = w32["reads_per_s"]; out["ms_per_step_int32"] = w32["ms_per_step"]; out["ms_per_step_int32_min_max"] = [w32["ms_per_step_min"], w32["ms_per_step_max"]]
             except Exception as e:
-                out["eight_logical_devices"] = {"error": str(e)[:300]}
-    if world > 1 and not args.no_extras:
-        # N > 1: the whole command line over the N devices (`yaha -gpus N`, one process, N x 3 contexts, index image uploaded to every device), the other ranks idle
-        try:
-            out["end_to_end"] = end_to_end(ya, idx, fa, cache, args.e2e_reads, 3000, gpus=min(world, max(1, torch.cuda.device_count())))
-            out["e2e_reads_per_s"] = out["end_to_end"]["e2e_reads_per_s"]; out["steady_reads_per_s"] = out["end_to_end"]["steady_reads_per_s"]
-        except Exception as e:
-            out["end_to_end"] = {"error": str(e)[:300]}
-    if world == 1 and not args.no_cpu_baseline:
-        try:
-            out["cpu_baseline"] = cpu_baseline(idx, fa, reads_path, n_reads, cache, args.cpu_seconds, args.read_len, args.div)
-        except Exception as e:  # the baseline is a reported number, never a reason to lose the measurement
-            out["cpu_baseline"] = {"value": None, "unit": "reads/s", "cores": os.cpu_count(), "kind": "error", "sample": str(e)[:200]}
-        cb = out["cpu_baseline"]
-        if cb.get("kind") == "reference" and cb.get("reference_sam"):
+                wl.append({"workload": "c2 int32", "error": str(e)[:200]})
+            finally:
+                del os.environ["YGPU_EXT32"]
             try:
-                e2e_path = os.path.join(cache, "e2e_n%d_l%d_s%d.fa" % (args.e2e_reads, args.read_len, 3000))
-                out["verified"] = verify_against_reference(ya, idx, cb, e2e_path if not args.no_extras else None, cache)
+                wl.append(config5_leg(ya, idx, fa, cache, local, args.contexts, "g%dm" % args.genome_mbp))
             except Exception as e:
-                out["verified"] = {"identical": False, "error": str(e)[:300]}
-            for k2 in ("sample_path", "reference_sam"):
-                cb.pop(k2, None)
-            v = out["verified"]
-            out["verified_identical"] = bool(v.get("identical")); out["verified_reads"] = int(v.get("reads") or 0) + int((v.get("e2e_sample") or {}).get("reads") or 0)
+                wl.append({"workload": "c5", "error": str(e)[:300]})
+            wl.insert(1, {"workload": "c2: 1 kbp reads, r=0.05 (realised 1.7%) = the headline", "reads_per_step": n_reads, "steps": steps, "reads_per_s": value, "bases_per_s": value * Lq, "ms_per_step": 1e3 * dt / steps,
+                          "k_ext_rows_ms_per_step": rows_dev_ms})
+            out["workloads"] = wl
+            for w in wl:      # (flat copies: the driver's record drops nested lists)
+                tag = (w.get("workload") or "")[:2]
+                if tag in ("c1", "c3", "c5") and w.get("reads_per_s"):
+                    out["value_" + tag] = w["reads_per_s"]
+                    if w.get("verified") is not None: out["verified_" + tag] = bool(w["verified"].get("identical")) if isinstance(w["verified"], dict) else bool(w["verified"])
+            try:
+                out["end_to_end"] = end_to_end(ya, idx, fa, cache, args.e2e_reads, 3000)
+                out["e2e_reads_per_s"] = out["end_to_end"]["e2e_reads_per_s"]; out["steady_reads_per_s"] = out["end_to_end"]["steady_reads_per_s"]
+                out["contexts_up_ms"] = out["end_to_end"].get("contexts_up_ms")
+                if args.e2e_reads >= 262144:     # BASELINE config 3's shape through the command line as well: 32 768 reads of 10 kbp (20 batches of ~16 M bases), r = 0.10 (realised 3.4 %)
+                    out["end_to_end_c3"] = end_to_end(ya, idx, fa, cache, 32768, 3100, read_len=10000, div=0.034, settle_s=40.0)
+                    out["e2e_c3_reads_per_s"] = out["end_to_end_c3"].get("e2e_reads_per_s"); out["steady_c3_reads_per_s"] = out["end_to_end_c3"].get("steady_reads_per_s")
+            except Exception as e:
+                out["end_to_end"] = {"error": str(e)[:200]}
+            try:
+                out["host_ceiling"] = host_ceiling(ya, idx, os.path.join(cache, "e2e_n%d_l%d_s%d.fa" % (args.e2e_reads, 1000, 3000)))
+                out["host_ceiling_reads_per_s"] = out["host_ceiling"]["host_ceiling_reads_per_s"]
+            except Exception as e:
+                out["host_ceiling"] = {"error": str(e)[:300]}
+            if args.e2e_reads >= 262144:
+                try:
+                    out["eight_logical_devices"] = eight_logical_devices(ya, cache, args.seed, args.e2e_reads)
+                except Exception as e:
+                    out["eight_logical_devices"] = {"error": str(e)[:300]}
+        if world > 1 and not args.no_extras:
+            # N > 1: the whole command line over the N devices (`yaha -gpus N`, one process, N x 3 contexts, index image uploaded to every device), the other ranks idle
+            try:
+                out["end_to_end"] = end_to_end(ya, idx, fa, cache, args.e2e_reads, 3000, gpus=min(world, max(1, torch.cuda.device_count())))
+                out["e2e_reads_per_s"] = out["end_to_end"]["e2e_reads_per_s"]; out["steady_reads_per_s"] = out["end_to_end"]["steady_reads_per_s"]
+            except Exception as e:
+                out["end_to_end"] = {"error": str(e)[:300]}
+        if world == 1 and not args.no_cpu_baseline:
+            try:
+                out["cpu_baseline"] = cpu_baseline(idx, fa, reads_path, n_reads, cache, args.cpu_seconds, args.read_len, args.div)
+            except Exception as e:  # the baseline is a reported number, never a reason to lose the measurement
+                out["cpu_baseline"] = {"value": None, "unit": "reads/s", "cores": os.cpu_count(), "kind": "error", "sample": str(e)[:200]}
+            cb = out["cpu_baseline"]
+            if cb.get("kind") == "reference" and cb.get("reference_sam"):
+                try:
+                    e2e_path = os.path.join(cache, "e2e_n%d_l%d_s%d.fa" % (args.e2e_reads, args.read_len, 3000))
+                    out["verified"] = verify_against_reference(ya, idx, cb, e2e_path if not args.no_extras else None, cache)
+                except Exception as e:
+                    out["verified"] = {"identical": False, "error": str(e)[:300]}
+                for k2 in ("sample_path", "reference_sam"):
+                    cb.pop(k2, None)
+                v = out["verified"]
+                out["verified_identical"] = bool(v.get("identical")); out["verified_reads"] = int(v.get("reads") or 0) + int((v.get("e2e_sample") or {}).get("reads") or 0)
     print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier(group=cpu_group)

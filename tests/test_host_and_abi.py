@@ -103,6 +103,44 @@ def test_bench_picks_the_genome_the_box_can_hold(tmp_path, monkeypatch):
     assert bench.pick_genome_mbp(str(tmp_path), 42) == 3100
 
 
+@pytest.mark.parametrize("max_bytes,max_reads", [(64 << 20, 2048), (64 << 20, 7), (96 << 10, 2048)])
+def test_bench_dump_outputs_hold_the_results_of_a_step(work, index11, tmp_path, max_bytes, max_reads):
+    """bench.py --dump-outputs: a ResultBatch (here the oracle's, which the device's equals bit for bit) written as float .npy files within the byte limit; the
+    sampled reads' clumps and edit ops read back to exactly what result_records gives, clump_start and the counters whole."""
+    import importlib, sys
+    import numpy as np
+    import oracle
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    with ya.Session(["-x", index11, "-q", os.path.join(work, "rchim.fa")]) as s:
+        b = s.next_batch(256)
+        r, _own = oracle.run(s.index, s.params, b, threads=4)
+        recs = ya.result_records(r)
+        out = str(tmp_path / "dump")
+        bench.dump_outputs(r, out, max_bytes=max_bytes, max_sample_reads=max_reads)
+        files = sorted(os.listdir(out))
+        assert files == ["clump_start.npy", "clumps.npy", "counters.npy", "ops.npy", "sample_reads.npy"]
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= max_bytes
+        d = {f[:-4]: np.load(os.path.join(out, f)) for f in files}
+        assert all(v.dtype in (np.float32, np.float64) for v in d.values())
+        assert d["counters"].tolist() == [float(v) for v in r.counters.as_dict().values()]
+        cs = d["clump_start"].astype(np.int64)
+        assert cs.tolist() == [r.clump_start[i] for i in range(r.n_reads + 1)]
+        sample = d["sample_reads"].astype(np.int64)
+        assert 0 < len(sample) <= min(max_reads, r.n_reads) and (np.diff(sample) > 0).all()
+        k = o = 0
+        for i in sample:
+            for rec in recs[i]:
+                row = d["clumps"][k]
+                ops = d["ops"][o:o + int(row[10])].astype(np.int64)
+                assert tuple(int(x) for x in row[:10]) == rec[:10] and tuple((int(x) & 0xFFFF, chr(int(x) >> 16)) for x in ops) == rec[10]
+                k += 1; o += len(ops)
+        assert k == len(d["clumps"]) and o == len(d["ops"])
+        # the same results give the same files
+        bench.dump_outputs(r, out + "2", max_bytes=max_bytes, max_sample_reads=max_reads)
+        assert all(np.array_equal(np.load(os.path.join(out + "2", f)), d[f[:-4]]) for f in files)
+
+
 def test_no_kernel_spills_vector_registers():
     """Every kernel of the built library keeps its vector registers out of scratch memory (tools/kernel_resources.py reads the code object's notes): round 4's 32-bit
     rows kernel spilled four and lost 1.2 %."""

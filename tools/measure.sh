@@ -12,7 +12,7 @@
 #  r03_n2_dryrun.sh, r03_oqc_prof.sh, ctx_sweep.sh, cli_probe.sh -- are modes of this one)
 MODE=$1; shift
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; cd $R; mkdir -p gpurun_out
-B="python bench.py --no-cpu-baseline --no-extras"
+B="python bench.py --full --no-cpu-baseline --no-extras"
 C=/tmp/yaha_bench_cache; X=$C/g3100m_s42.X15_01_65525S
 line() { python -c "import json,sys; j=json.loads(sys.stdin.read().strip().split('\n')[-1]); print('$1', round(j['value']), round(j['ms_per_step'],2))"; }
 warm() { $B --steps 2 --warmup 1 > /dev/null 2>&1; }
@@ -63,19 +63,19 @@ clienv)
   for x in "$@"; do sleep 25; env $V=$x YAHA_STATS=1 yaha_amd/csrc/yaha -x $X -q $R1 -osh /dev/shm/o.sam 2>&1 | grep "stats" | sed "s/^/[$V=$x] /" | cut -c1-700 | tee -a gpurun_out/$TAG.txt; done
   rm -f /dev/shm/o.sam ;;
 n2)
-  TAG=${1:-n2}
-  YAHA_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 4 --warmup 1 --genome-mbp 100 --contexts 1 --e2e-reads 65536 > gpurun_out/$TAG.json 2> gpurun_out/$TAG.err; echo "rc $?"
-  tail -5 gpurun_out/$TAG.err | cut -c1-300
-  python - gpurun_out/$TAG.json <<'PY'
+  TAG=${1:-n2}; D=$(mktemp -d); trap 'rm -rf "$D"' EXIT; J=$D/$TAG
+  YAHA_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 4 --warmup 1 --genome-mbp 100 --contexts 1 --e2e-reads 65536 --full > $J.json 2> $J.err; echo "rc $?"
+  tail -5 $J.err | cut -c1-300
+  python - $J.json <<'PY'
 import json, sys; j = json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])
 print({k: j.get(k) for k in ('n_gpus', 'value', 'ms_per_step', 'e2e_reads_per_s', 'steady_reads_per_s')}); print(j.get('end_to_end'))
 PY
   ;;
 oqc)
   TAG=${1:-oqc}
-  YGPU_OQC_PROF=1 python bench.py --steps 2 --warmup 1 --contexts 1 --no-cpu-baseline --e2e-reads 16384 2>&1 >/dev/null | grep "post-filter class" | tail -5
+  YGPU_OQC_PROF=1 python bench.py --steps 2 --warmup 1 --contexts 1 --full --no-cpu-baseline --e2e-reads 16384 2>&1 >/dev/null | grep "post-filter class" | tail -5
   O=$R/gpurun_out/$TAG; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-  rocprofv3 --output-format csv --kernel-trace --stats -d $O/stats -o stats -- python3 $R/bench.py --steps 4 --warmup 1 --contexts 1 --no-cpu-baseline --e2e-reads 16384 > $O/bench.json 2> $O/bench.err
+  rocprofv3 --output-format csv --kernel-trace --stats -d $O/stats -o stats -- python3 $R/bench.py --steps 4 --warmup 1 --contexts 1 --full --no-cpu-baseline --e2e-reads 16384 > $O/bench.json 2> $O/bench.err
   kernel_table $O/stats 5 | grep -E "sum of|k_oqc" ;;
 *) echo "unknown mode $MODE"; exit 2 ;;
 esac

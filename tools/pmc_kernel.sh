@@ -3,7 +3,7 @@
 export KSUB=${1:-k_seg_sort}; TAG=${2:-pmc_kernel}
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/$TAG; export OUT; mkdir -p $OUT
-B="python3 $R/bench.py --no-cpu-baseline --no-extras"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-extras"
 $B --steps 1 --warmup 0 > $OUT/warm.json 2> $OUT/warm.err
 pass() { name=$1; shift; timeout 300 rocprofv3 --output-format csv --kernel-trace --pmc "$@" -d $OUT/$name -o $name -- $B --steps 1 --warmup 0 --contexts 1 > $OUT/$name.json 2> $OUT/$name.err || echo "pass $name failed"; }
 pass sq SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU

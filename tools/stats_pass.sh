@@ -3,8 +3,8 @@
 TAG=${1:-stats}; READS=${2:-8192}
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
-python3 $R/bench.py --reads-per-gpu $READS --steps 1 --warmup 0 --no-cpu-baseline > $OUT/warm.json 2> $OUT/warm.err
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats -o stats -- python3 $R/bench.py --reads-per-gpu $READS --steps 3 --warmup 1 --no-cpu-baseline > $OUT/stats.json 2> $OUT/stats.err
+python3 $R/bench.py --reads-per-gpu $READS --steps 1 --warmup 0 --no-cpu-baseline --full > $OUT/warm.json 2> $OUT/warm.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats -o stats -- python3 $R/bench.py --reads-per-gpu $READS --steps 3 --warmup 1 --no-cpu-baseline --full > $OUT/stats.json 2> $OUT/stats.err
 python3 - <<PY
 import csv
 rows=list(csv.DictReader(open("$OUT/stats/stats_kernel_stats.csv")))
