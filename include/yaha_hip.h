@@ -208,6 +208,30 @@ int  ygpu_postfilter_drop(ygpu_ctx *ctx);                                      /
 int  ygpu_filtered_size(ygpu_ctx *ctx, uint64_t *n_clumps, uint64_t *n_ops);
 int  ygpu_collect_filtered(ygpu_ctx *ctx, uint32_t *clump_start, ygpu_out_clump *clumps, uint32_t *ops, ygpu_filtered_batch *out);
 
+/* ---- read depth along the reference (optional, behind ygpu_postfilter) ------------------------------------------------------------------------------------
+ * Structural-variant callers combine split reads -- the SAM -- with read depth.  After the post-filter the clumps that will be printed, their edit ops and the
+ * sequence table are all on the device, so depth is accumulated there: with ygpu_depth_enable, every ygpu_postfilter of the context also adds the clumps it
+ * returns to a binned coverage array (uint32 per bin; the reference has no counterpart, its users run a second tool over the sorted SAM).
+ * The contract (yaha_amd/csrc/depth_core.h -- one routine for host and device): every sequence is cut into bins of `bin` bases, never across two sequences, the
+ * last bin of a sequence may be shorter, bins are numbered sequence by sequence in index order: n_bins = sum of ceil(length / bin).  cov[b] = number of
+ * (record, reference base) pairs in bin b over the records yaha_session_emit_filtered prints: the bases under M and R ops (the M of the printed CIGAR), not those
+ * under D; a clump that spans two sequences is not printed and covers nothing; records with mapQuality < min_mapq cover nothing.  A bin that passes 2^32 - 1
+ * wraps (not handled).  Reads that come back UNFILTERED (more than 1 792 clumps, primaryCount == 0xFFFF) are NOT counted: the caller filters them and counts
+ * what it prints.
+ * ONE array per index image, 4 * n_bins bytes of device memory: the contexts that share an image (ygpu_clone, ctx_per_device of ygpu_init_multi) add into the
+ * same array (global atomics) once each of them has called ygpu_depth_enable with the same parameters -- the first call makes and zeroes it, the others join.
+ * When it does not fit: YGPU_ENOMEM, the sizes in ygpu_last_error (bin 1 on a 3.1 Gbp genome is 12.4 GB).  It lives until the last of those contexts is destroyed;
+ * ygpu_park of one of them does not touch it.  Order: ygpu_set_postfilter, ygpu_depth_enable, then batches (ygpu_run, ygpu_postfilter ...), ygpu_depth_collect. */
+typedef struct ygpu_depth_params {
+    uint32_t bin, min_mapq, n_seqs;
+    const uint32_t *seq_start, *seq_length;            /* reference sequences in bases, ascending (host memory; copied) */
+} ygpu_depth_params;
+int  ygpu_depth_enable(ygpu_ctx *ctx, const ygpu_depth_params *p);             /* after ygpu_set_postfilter */
+int  ygpu_depth_size(ygpu_ctx *ctx, uint64_t *n_bins);
+/* The image's array as it stands, into bins[n_bins] (may be NULL): waits for every filter stage queued so far on the device, its sibling contexts' included.
+ * stats (may be NULL): records counted, records skipped (MAPQ), records dropped (two sequences), reads left to the caller (handed back unfiltered). */
+int  ygpu_depth_collect(ygpu_ctx *ctx, uint32_t *bins, uint64_t stats[4]);
+
 /* Stage-level entry for tests of the post-filter (as ygpu_dp_batch is for the DP kernels): place a result batch on the device as if ygpu_run had produced it
  * for the reads uploaded last (r->n_reads must equal the uploaded batch's; clump_start / clumps / ops as ygpu_collect returns them).  ygpu_postfilter,
  * ygpu_collect and their siblings then work on it -- so that the device filter can be driven with clump lists no real read produces (hundreds of exact ties,
@@ -309,6 +333,9 @@ int  yaha_session_emit(yaha_session *s, const ygpu_result_batch *r, const char *
  * ygpu_collect_filtered returned.  yaha_session_emit(ygpu_collect(...)) and yaha_session_emit_filtered(ygpu_collect_filtered(...)) give the same text. */
 int  yaha_session_postfilter_params(yaha_session *s, ygpu_postfilter_params *p);
 int  yaha_session_emit_filtered(yaha_session *s, const ygpu_filtered_batch *r, const char **text, size_t *len);
+/* Bin size (-covbin, default 100), least mapping quality (-covq, default 0) and the sequence table for ygpu_depth_enable, from the session's arguments
+ * (pointers into the session, valid until it is closed). */
+int  yaha_session_depth_params(yaha_session *s, ygpu_depth_params *p);
 /* `yaha -g genome.fa [-L k] [-S s] [-H h]`: writes genome.nib2 and genome.X<LL>_<SS>_<HHHHH>S (Main.c:554-628). */
 int  yaha_build_index(int argc, const char *const *argv);
 /* The complete command-line program (index creation or query alignment on the GPU). */

@@ -72,6 +72,13 @@ class PostfilterParams(C.Structure):
                 ("bppVmin", C.c_int32), ("bppN", C.c_int32), ("bppThr", C.c_void_p), ("n_seqs", C.c_uint32), ("seq_start", C.c_void_p), ("seq_length", C.c_void_p)]
 
 
+class DepthParams(C.Structure):
+    _fields_ = [("bin", C.c_uint32), ("min_mapq", C.c_uint32), ("n_seqs", C.c_uint32), ("seq_start", C.c_void_p), ("seq_length", C.c_void_p)]
+
+
+DEPTH_STATS = ("records_counted", "records_skipped_mapq", "records_dropped_two_sequences", "reads_left_to_host")
+
+
 class OutClump(C.Structure):
     _fields_ = [("c", Clump), ("status", C.c_uint8), ("mapQuality", C.c_uint8), ("numSecondaries", C.c_uint16), ("matchedPrimary", C.c_uint16), ("primaryCount", C.c_uint16)]
 
@@ -90,6 +97,7 @@ DP_KERNELS_AUTO, DP_KERNELS_WAVE, DP_KERNELS_LANES, DP_KERNELS_LANES_CAREFUL = 0
 
 EXPORTS = (
     "ygpu_device_count", "ygpu_init", "ygpu_init_multi", "ygpu_clone", "ygpu_destroy", "ygpu_last_error", "ygpu_memory", "ygpu_park", "ygpu_get_arena_profile", "ygpu_presize", "ygpu_upload", "ygpu_upload_nowait", "ygpu_run", "ygpu_collect", "ygpu_result_size", "ygpu_collect_into", "ygpu_host_alloc", "ygpu_host_free", "ygpu_set_postfilter", "ygpu_postfilter_snapshot", "ygpu_postfilter", "ygpu_postfilter_drop", "ygpu_inject_results", "ygpu_selftest_primitives", "ygpu_trace_volume", "ygpu_filtered_size", "ygpu_collect_filtered", "ygpu_last_timing",
+    "ygpu_depth_enable", "ygpu_depth_size", "ygpu_depth_collect", "yaha_session_depth_params",
     "ygpu_submit", "ygpu_poll", "ygpu_wait", "ygpu_seed_join", "ygpu_chain", "ygpu_dp_batch", "ygpu_dp_batch_ex",
     "yaha_session_open", "yaha_session_close", "yaha_session_error", "yaha_session_params",
     "yaha_session_index_view", "yaha_session_header", "yaha_session_next_batch", "yaha_session_emit", "yaha_session_postfilter_params", "yaha_session_emit_filtered",
@@ -260,6 +268,23 @@ class Context:
         if lib().yaha_session_postfilter_params(session._h, C.byref(p)) != 0:
             raise RuntimeError("yaha_session_postfilter_params: " + lib().yaha_session_error(session._h).decode())
         self._check(lib().ygpu_set_postfilter(self._h, C.byref(p)), "ygpu_set_postfilter")
+
+    def depth_enable(self, session):
+        """Read depth of the printed clumps behind postfilter() (ygpu_depth_enable), with the session's -covbin / -covq and sequence table.  After
+        set_postfilter(); the contexts of one index image share one array."""
+        p = DepthParams()
+        if lib().yaha_session_depth_params(session._h, C.byref(p)) != 0:
+            raise RuntimeError("yaha_session_depth_params: " + lib().yaha_session_error(session._h).decode())
+        self._check(lib().ygpu_depth_enable(self._h, C.byref(p)), "ygpu_depth_enable")
+
+    def depth_collect(self):
+        """(coverage array of the context's index image as it stands -- one uint32 per bin, a numpy array -- and the statistics as a dict)."""
+        import numpy as np
+        n = C.c_uint64()
+        self._check(lib().ygpu_depth_size(self._h, C.byref(n)), "ygpu_depth_size")
+        bins = np.zeros(max(1, n.value), dtype=np.uint32); st = (C.c_uint64 * 4)()
+        self._check(lib().ygpu_depth_collect(self._h, bins.ctypes.data_as(C.POINTER(C.c_uint32)), st), "ygpu_depth_collect")
+        return bins[:n.value], {k: int(st[i]) for i, k in enumerate(DEPTH_STATS)}
 
     def inject_results(self, result):
         """Stage-level test entry: a ResultBatch placed on the device as if ygpu_run had produced it for the uploaded reads."""

@@ -36,6 +36,7 @@
 #include <thread>
 #include <mutex>
 #include <condition_variable>
+#include <memory>
 #include "common.h"
 #include "../oqc_core.h"
 
@@ -114,6 +115,18 @@ struct PfSide {
     int device = 0;
 };
 
+// Read depth along the reference (-ocov; depth_stage.h, ../depth_core.h): ONE coverage array per index image -- 4 bytes a bin -- which the contexts that share
+// the image (ygpu_clone, ctx_per_device of ygpu_init_multi) feed together with global atomics.  Made by the first ygpu_depth_enable of the image, held by every
+// context that enabled it, released with the last of them (never by ygpu_park: a parked sibling keeps its reference and gives up nothing of the image's).
+struct DepthImage {
+    int device = 0;
+    DevBuf cov, stats, seqStart, seqLength, binBase;
+    uint64_t nBins = 0;
+    uint32_t bin = 0, minMapq = 0;
+    std::vector<uint32_t> hSeqStart, hSeqLength;                  // what it was enabled with (a second enable must agree)
+    ~DepthImage() { (void)hipSetDevice(device); cov.release(); stats.release(); seqStart.release(); seqLength.release(); binBase.release(); }
+};
+
 struct ygpu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -187,6 +200,7 @@ struct ygpu_ctx {
     DevCounters snapCtrPlain{};
     unsigned long long snapHits = 0, snapFrags = 0, snapRegions = 0;
     DevBuf oqCs, oqCl, oqOpsIn, oqSeeds, oqQlen;
+    std::shared_ptr<DepthImage> depth;           // set by ygpu_depth_enable: the post-filter then feeds the image's coverage array
     // stage state
     uint32_t hOutCounts[2] = {0, 0}, hOutEf = 0;
     bool hOutValid = false;

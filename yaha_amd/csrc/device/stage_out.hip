@@ -1,7 +1,10 @@
 // stage_out.hip -- what leaves the device: the batch's results as ygpu_run left them (ygpu_collect*), and the post-filter stage (postFilterBySimilarity,
-// GraphPath.cpp:897-1086, Query.c:450) on a snapshot of them -- oqc_stage.h -- with its own stream, wait slot and look-back words (PfSide).
+// GraphPath.cpp:897-1086, Query.c:450) on a snapshot of them -- oqc_stage.h -- with its own stream, wait slot and look-back words (PfSide); behind it, when
+// ygpu_depth_enable asked for it, the read-depth track of the printed clumps (depth_stage.h).
 #include "ctx.h"
 #include "oqc_stage.h"
+#include "depth_stage.h"
+#include <map>
 
 extern "C" {
 int ygpu_collect(ygpu_ctx *ctx, ygpu_result_batch *out)
@@ -187,6 +190,15 @@ static int postfilterBody(ygpu_ctx *full)
     ENSURE(full->oqFClumps, sizeof(ygpu_out_clump) * ((uint64_t)tot[0] + 1)); ENSURE(full->oqFOps, 4ull * ((uint64_t)tot[1] + 1));
     KL(k_oqc_gather, dim3(gridFor((uint64_t)n * 64, 256)), dim3(256), 0, ctx->stream, A, full->oqOutStart.as<uint32_t>(), full->oqOpsStart.as<uint32_t>(),
         full->oqFClumps.as<ygpu_out_clump>(), full->oqFOps.as<uint32_t>());
+    // read depth (-ocov): the clumps just gathered are the ones that get printed -- a wave each adds what it covers to the image's array, on this stage's stream
+    if (full->depth && tot[0]) {
+        DepthImage &DI = *full->depth; DepthArgs D;
+        D.L.seqStart = DI.seqStart.as<uint32_t>(); D.L.seqLength = DI.seqLength.as<uint32_t>(); D.L.binBase = DI.binBase.as<uint32_t>();
+        D.L.nSeqs = (uint32_t)DI.hSeqStart.size(); D.L.bin = DI.bin; D.L.minMapq = DI.minMapq;
+        D.cov = DI.cov.as<uint32_t>(); D.nBins = (uint32_t)DI.nBins; D.stats = DI.stats.as<unsigned long long>();
+        KL(k_depth_clumps, dim3(gridFor((uint64_t)tot[0] * 64, 256)), dim3(256), 0, ctx->stream, D, full->oqFClumps.as<ygpu_out_clump>(), full->oqFOps.as<uint32_t>(), tot[0]);
+        KL(k_depth_handed_back, dim3(gridFor(n, 256)), dim3(256), 0, ctx->stream, full->oqOutCnt.as<uint32_t>(), full->oqPrimCnt.as<uint32_t>(), n, D.stats);
+    }
     if (oqProf) {
         unsigned long long h[32 * YQ_NCLASS]; HIPCHK(hipMemcpyAsync(h, full->oqProf.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
         static const char *nm[7] = {"keys", "sort", "dup scan", "nodes+tables", "path walk", "successors", "finish"};
@@ -199,6 +211,65 @@ static int postfilterBody(ygpu_ctx *full)
         }
     }
     full->oqDone = true;
+    return 0;
+}
+// ---- read depth along the reference (depth_stage.h; the contract is in ../depth_core.h) ---------------------------------------------------------------------
+// the coverage arrays of this process, by the image they belong to (the address of its bases on the device: what the contexts of an image share)
+static std::mutex gDepthMu;
+static std::map<std::pair<int, const void *>, std::weak_ptr<DepthImage>> gDepthImages;
+int ygpu_depth_enable(ygpu_ctx *ctx, const ygpu_depth_params *p)
+{
+    if (!ctx || !ctx->stream || !p) return YGPU_EINVAL;
+    if (!ctx->oqSet) { ctx->err = "ygpu_depth_enable: ygpu_set_postfilter has not been called on this context (depth is counted behind the post-filter)"; return YGPU_EINVAL; }
+    if (p->bin < 1 || !p->n_seqs || !p->seq_start || !p->seq_length) { ctx->err = "ygpu_depth_enable: bad bin size or sequence table";
+        return YGPU_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    std::lock_guard<std::mutex> lk(gDepthMu);
+    const std::pair<int, const void *> key(ctx->device, ctx->dBases.p);
+    if (std::shared_ptr<DepthImage> have = gDepthImages[key].lock()) {      // a sibling enabled it: the same array, if the same track is asked for
+        if (have->bin != p->bin || have->minMapq != p->min_mapq || have->hSeqStart.size() != p->n_seqs
+            || memcmp(have->hSeqStart.data(), p->seq_start, 4ull * p->n_seqs) != 0 || memcmp(have->hSeqLength.data(), p->seq_length, 4ull * p->n_seqs) != 0) {
+            ctx->err = "ygpu_depth_enable: the image's coverage array was enabled with other parameters"; return YGPU_EINVAL; }
+        ctx->depth = have; return 0;
+    }
+    std::shared_ptr<DepthImage> DI(new DepthImage); DI->device = ctx->device; DI->bin = p->bin; DI->minMapq = p->min_mapq;
+    DI->hSeqStart.assign(p->seq_start, p->seq_start + p->n_seqs); DI->hSeqLength.assign(p->seq_length, p->seq_length + p->n_seqs);
+    std::vector<uint32_t> binBase(p->n_seqs + 1);
+    if (!ydepth::layoutBins(p->seq_length, p->n_seqs, p->bin, binBase.data(), &DI->nBins) || DI->nBins == 0) { ctx->err = "ygpu_depth_enable: the bins do not fit 32 bits";
+        return YGPU_EINVAL; }
+    // (exact: a growth margin on 12 GB is 3 GB)
+    if (DI->cov.ensureExact(4ull * DI->nBins)) {
+        (void)hipGetLastError(); size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) != hipSuccess) { fb = 0; (void)hipGetLastError(); }
+        char m[256]; snprintf(m, sizeof m, "ygpu_depth_enable: no room on device %d for the coverage array: %.2f GB for %llu bins of %u bases, %.2f GB free "
+            "(a larger -covbin needs less)", ctx->device, 4.0 * DI->nBins / 1e9, (unsigned long long)DI->nBins, p->bin, fb / 1e9);
+        ctx->err = m; return YGPU_ENOMEM;
+    }
+    if (DI->stats.ensure(64) || DI->seqStart.ensure(4ull * p->n_seqs) || DI->seqLength.ensure(4ull * p->n_seqs) || DI->binBase.ensure(4ull * (p->n_seqs + 1))) {
+        (void)hipGetLastError(); ctx->err = "ygpu_depth_enable: hipMalloc failed"; return YGPU_ENOMEM; }
+    HIPCHK(hipMemsetAsync(DI->cov.p, 0, 4ull * DI->nBins, ctx->stream)); HIPCHK(hipMemsetAsync(DI->stats.p, 0, 64, ctx->stream));
+    HIPCHK(hipMemcpyAsync(DI->seqStart.p, p->seq_start, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(DI->seqLength.p, p->seq_length, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(DI->binBase.p, binBase.data(), 4ull * (p->n_seqs + 1), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(streamSync(ctx));
+    gDepthImages[key] = DI; ctx->depth = DI;
+    return 0;
+}
+int ygpu_depth_size(ygpu_ctx *ctx, uint64_t *n_bins)
+{
+    if (!ctx || !n_bins) return YGPU_EINVAL;
+    if (!ctx->depth) { ctx->err = "ygpu_depth_size: ygpu_depth_enable has not been called on this context"; return YGPU_EINVAL; }
+    *n_bins = ctx->depth->nBins; return 0;
+}
+// The image's array as it stands: every filter stage queued on the device so far -- this context's and its siblings' -- has finished when the copy is taken.
+int ygpu_depth_collect(ygpu_ctx *ctx, uint32_t *bins, uint64_t stats[4])
+{
+    if (!ctx || !ctx->stream) return YGPU_EINVAL;
+    if (!ctx->depth) { ctx->err = "ygpu_depth_collect: ygpu_depth_enable has not been called on this context"; return YGPU_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipDeviceSynchronize());
+    DepthImage &DI = *ctx->depth;
+    if (bins) HIPCHK(hipMemcpy(bins, DI.cov.p, 4ull * DI.nBins, hipMemcpyDeviceToHost));
+    if (stats) { unsigned long long h[4]; HIPCHK(hipMemcpy(h, DI.stats.p, sizeof h, hipMemcpyDeviceToHost)); for (int k = 0; k < 4; k++) stats[k] = h[k]; }
     return 0;
 }
 int ygpu_inject_results(ygpu_ctx *ctx, const ygpu_result_batch *r)

@@ -1,7 +1,8 @@
 // args.cpp -- command line, defaults and derived parameters.  Same option names, defaults, value checks and
 // file-name derivation as the reference CLI (Main.c:187-565, AlignArgs.c:27-169) so that
 // `yaha -g genome.fa` / `yaha -x index -q reads ...` keep working unchanged.  Extra options of this
-// implementation: -gpus N (shard batches over N devices), -ctx M (contexts per device), -device D, -batch N (reads per device batch).
+// implementation: -gpus N (shard batches over N devices), -ctx M (contexts per device), -device D, -batch N (reads per device batch),
+// -ocov FILE / -covbin B / -covq Q (read depth of the printed records as bedGraph).
 #include "yaha_host.h"
 #include <cstring>
 #include <cstdlib>
@@ -22,7 +23,11 @@ static void usage(FILE *o)
           "  general : [-BW 5] [-G 50] [-H 650] [-M 25] [-MD 50] [-P 0.9] [-X 25]\n"
           "  scoring : [-AGS Y|N] [-GEC 2] [-GOC 5] [-MS 1] [-RC 3]\n"
           "  OQC     : [-OQC Y|N] [-BP 5] [-MGDP 5] [-MNO minMatch]   FBS: [-FBS Y|N] [-PRL 0.9] [-PSS 0.9]\n"
-          "  -o8 modified Blast8, -osh SAM hard clipping, -oss SAM soft clipping.\n", o);
+          "  -o8 modified Blast8, -osh SAM hard clipping, -oss SAM soft clipping.\n"
+          "  depth   : [-ocov depthFile|stdout] [-covbin basesPerBin (100)] [-covq minMapQ (0)]\n"
+          "       read depth of the printed records along the reference (bases under M of the CIGAR) as bedGraph, written after the last alignment;\n"
+          "       accumulated on the device behind its post-filter: 4 bytes a bin of device memory per GPU -- -covbin 1 on a 3.1 Gbp genome is 12.4 GB beside the\n"
+          "       contexts' arenas; when that does not fit the run stops before the first batch and says so (use a larger bin or a smaller -ctx).\n", o);
 }
 
 static bool parseBool(const char *s, const char *key, bool &out)
@@ -97,9 +102,19 @@ int parseArgs(int argc, char **argv, Args &a)
         else if (is("-batch")) { if (!parseInt(val(), "-batch", a.batchReads)) return 2;
                                  if (a.batchReads < 1 || a.batchReads > 65536) { fprintf(stderr, "-batch must be between 1 and 65536 (reads per device batch).\n\n"); usage(stderr);
                                      return 2; } }
+        else if (is("-ocov")) { const char *v = val(); a.covFileName = (!strcmp(v, "-stdout")) ? "stdout" : v; a.haveCov = true;
+            if (a.covFileName.empty()) { fprintf(stderr, "-ocov needs a file name.\n\n"); usage(stderr); return 3; } }
+        else if (is("-covbin")) { if (!parseInt(val(), "-covbin", a.covBin)) return 3; a.haveCovBin = true;
+            if (a.covBin < 1) { fprintf(stderr, "-covbin must be at least 1 (bases per bin).\n\n"); usage(stderr); return 3; } }
+        else if (is("-covq")) { if (!parseInt(val(), "-covq", a.covMinQ)) return 3; a.haveCovQ = true; }
         else { fprintf(stderr, "%s is not a valid option.\n\n", k); usage(stderr); return 2; }
     }
     a.query = query; a.index = index && !query;
+    // the read-depth track (exit code 2 for its errors): a query run's output only, its options need it, and it cannot share standard output with the alignments
+    if (!a.haveCov && (a.haveCovBin || a.haveCovQ)) { fprintf(stderr, "-covbin and -covq need -ocov.\n\n"); usage(stderr); return 3; }
+    if (a.haveCov && !query) { fprintf(stderr, "-ocov is an output of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return 3; }
+    if (a.haveCov && a.covFileName == "stdout" && (!a.haveO || a.ofileName == "stdout")) {
+        fprintf(stderr, "-ocov stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
     if ((a.compress || a.uncompress) && !query) {                                                  // Main.c:472-533: -c wants a FASTA genome, -u a .nib2
         if (!a.haveG) { fprintf(stderr, "Genome file specification (-g) is required for index creation.\n\n"); usage(stderr); return 2; }
         size_t dot = a.gfileName.rfind('.'); const std::string ext = dot == std::string::npos ? "" : a.gfileName.substr(dot);
@@ -165,6 +180,7 @@ std::string samHeader(const Args &a, const Genome &g)                   // outpu
         snprintf(buf, sizeof buf, " -OQC Y -BP %d -MGDP %d -MNO %d", a.BPCost, a.maxBPLog, a.OQCMinNonOverlap); h += buf;
         if (a.FBS) { snprintf(buf, sizeof buf, " -FBS Y -PRL %4.2f -PSS %4.2f", a.FBS_PSLength, a.FBS_PSScore); h += buf; } else h += " -FBS N";
     } else h += " -OQC N";
+    if (a.haveCov) { snprintf(buf, sizeof buf, " -covbin %d -covq %d", a.covBin, a.covMinQ); h += " -ocov " + a.covFileName + buf; }
     h += "\n";
     return h;
 }

@@ -25,6 +25,7 @@ struct yaha_session {
     std::vector<uint32_t> pfThr, pfSeqStart, pfSeqLen;               // what yaha_session_postfilter_params points into
     std::vector<Read> reads; std::vector<uint8_t> codes; std::vector<uint64_t> offsets;
     bool readerOpen = false;
+    DepthTrack *depth = nullptr;                                     // -ocov (the command line): the formatters add the records the device did not count
 };
 
 namespace yaha {
@@ -127,11 +128,12 @@ static void formatRange(const yaha_session *s, const ygpu_result_batch *r, uint3
     for (uint32_t i = i0; i < i1; i++) {
         uint32_t c0 = r->clump_start[i], c1 = r->clump_start[i + 1]; int primaryCount = 0;
         postFilter(a, s->genome, s->reads[i], r->clumps + c0, c1 - c0, r->ops, oc, primaryCount);
-        for (auto &o : oc) printClump(a, s->genome, s->reads[i], o, primaryCount, text);
+        for (auto &o : oc) { printClump(a, s->genome, s->reads[i], o, primaryCount, text); if (s->depth) s->depth->add(o); }
     }
 }
 // SAM text of a batch whose post-filter ran on the device (ygpu_postfilter): the clumps arrive in print order with the filter's fields set
-static void formatFiltered(const yaha_session *s, const ygpu_filtered_batch *r, Text &text)
+// (depthOnDevice: the device stage counted the batch's read depth as well -- all but the reads it handed back unfiltered)
+static void formatFiltered(const yaha_session *s, const ygpu_filtered_batch *r, Text &text, bool depthOnDevice = false)
 {
     const Args &a = s->args; text.clear();
     std::vector<ygpu_clump> raw; std::vector<OutClump> oc;
@@ -142,7 +144,7 @@ static void formatFiltered(const yaha_session *s, const ygpu_filtered_batch *r, 
             raw.resize(k1 - k0); for (uint32_t k = k0; k < k1; k++) raw[k - k0] = r->clumps[k].c;
             int primaryCount = 0;
             postFilter(a, s->genome, s->reads[i], raw.data(), k1 - k0, r->ops, oc, primaryCount);
-            for (auto &o : oc) printClump(a, s->genome, s->reads[i], o, primaryCount, text);
+            for (auto &o : oc) { printClump(a, s->genome, s->reads[i], o, primaryCount, text); if (s->depth) s->depth->add(o); }
             continue;
         }
         for (uint32_t k = k0; k < k1; k++) {
@@ -150,6 +152,7 @@ static void formatFiltered(const yaha_session *s, const ygpu_filtered_batch *r, 
             OutClump o; o.c = f.c; o.ops = r->ops + f.c.op_start; o.status = f.status; o.mapQuality = f.mapQuality; o.numSecondaries = f.numSecondaries;
                 o.matchedPrimary = f.matchedPrimary;
             printClump(a, s->genome, s->reads[i], o, (int)f.primaryCount, text);
+            if (s->depth && !depthOnDevice) s->depth->add(o);
         }
     }
 }
@@ -209,6 +212,9 @@ int runQueries(Args &a, FILE *log)
     Args &A = S->args;
     FILE *out = (A.ofileName == "stdout") ? stdout : fopen(A.ofileName.c_str(), "w");
     if (!out) { fprintf(log, "Failure to open output file: %s.\n", A.ofileName.c_str()); return 1; }
+    // -ocov: the host's coverage array (depth.cpp); the device stage behind the post-filter feeds one of its own per index image, merged at the end
+    std::unique_ptr<DepthTrack> depth;
+    if (A.haveCov) { depth.reset(new DepthTrack); if (!depth->init(S->genome, A.covBin, A.covMinQ, S->err)) { fprintf(log, "%s\n", S->err.c_str()); return 1; } }
     setvbuf(out, nullptr, _IONBF, 0);                                       // whole batches are written with one call each
     if (fputs(S->header.c_str(), out) < 0) { fprintf(log, "Failure writing the output file.\n"); return 1; }
     ygpu_params P; paramsFromArgs(A, P);
@@ -244,7 +250,7 @@ int runQueries(Args &a, FILE *log)
         }
     };
     struct Batch { uint64_t ticket = 0; std::vector<Span> spans; std::vector<Read> reads; size_t nReads = 0; std::vector<uint8_t> codes; std::vector<uint64_t> offsets;
-                   ResBuf clumpStart, ops, clumps; uint64_t nClumps = 0, nOps = 0; bool filtered = false; Text text; double tRead = 0, tDev = 0, tFmt = 0; };
+                   ResBuf clumpStart, ops, clumps; uint64_t nClumps = 0, nOps = 0; bool filtered = false, depthOnDevice = false; Text text; double tRead = 0, tDev = 0, tFmt = 0; };
     typedef std::unique_ptr<Batch> BatchP;
     struct Pool { std::mutex mu; std::vector<BatchP> free; BatchP get() { { std::lock_guard<std::mutex> lk(mu); if (!free.empty()) { BatchP b = std::move(free.back());
         free.pop_back(); return b; } } return BatchP(new Batch); }
@@ -315,6 +321,10 @@ int runQueries(Args &a, FILE *log)
         bool claimed = false, measured = false, haveProfile = false; ygpu_arena_profile profile; };
     std::vector<std::unique_ptr<Warm>> warm; for (int k = 0; k < nDev; k++) warm.emplace_back(new Warm);
     std::atomic<int> ctxUp(0), parked(0); double tCtxUp = 0;
+    // read depth on the device: one array per index image, enabled by every context of the image (the first makes it); depthCtx[k] = 1 + a context of device k
+    // that feeds it.  Without the entry points (a build without them) or when the stage is refused, the formatters count everything.
+    const bool depthDevice = depth && deviceFilter && DepthTrack::deviceEntryPoints() && getenv("YAHA_HOST_DEPTH") == nullptr;
+    std::vector<std::atomic<int>> depthCtx(nDev); for (auto &x : depthCtx) x = 0;
     std::vector<std::atomic<uint64_t>> devReads(nDev); for (auto &x : devReads) x = 0;       // reads each device took (the stats line: do all devices pull their weight?)
     // where a context thread's time goes, batches after a context's first (the stats line; microseconds): upload, run, waiting for the filter thread, snapshot; and the filter
     // thread's post-filter + collect
@@ -342,6 +352,14 @@ int runQueries(Args &a, FILE *log)
         }
         { std::unique_lock<std::mutex> lk(W.mu); W.cv.wait(lk, [&] { return W.ready != 0; }); rc0 = W.ready == 1 ? 0 : (leadRc[d / perDev] ? leadRc[d / perDev] : YGPU_ENODEV); }
         if (rc0 == 0 && deviceFilter) rc0 = ygpu_set_postfilter(ctx[d], &PF);
+        bool ctxDepth = false;
+        if (rc0 == 0 && depthDevice) {
+            const int rcD = depth->deviceEnable(ctx[d]);
+            // no room for the array beside the image and the arenas: the run stops here, before its first batch, with the sizes (a host array would hide that the
+            // device is full; a larger -covbin is the way out).  Any other refusal: this context's records are counted by the formatters.
+            if (rcD == YGPU_ENOMEM) { char m[640]; snprintf(m, sizeof m, "-ocov: %s", ygpu_last_error(ctx[d])); fail(m); }
+            else if (rcD == 0) { ctxDepth = true; int none = 0; depthCtx[d / perDev].compare_exchange_strong(none, d + 1); }
+        }
         if (rc0 != 0) { char m[512];
             snprintf(m, sizeof m, "ygpu_init(device %d) failed: %d %s", dev, rc0, ctx[d] ? ygpu_last_error(ctx[d]) : (d == leadCtx ? "" : "(the device's first context failed)"));
             fail(m); }
@@ -434,7 +452,7 @@ int runQueries(Args &a, FILE *log)
                 // (the batch lives until it is printed: no wait for its bytes here)
                 int rc = ygpu_upload_nowait(ctx[d], &rb); const double h1 = now(); if (rc == 0) rc = ygpu_run(ctx[d]); if (rc != 0) return rc;
                 const double h2 = now();
-                uint64_t nc = 0, no = 0; b->filtered = deviceFilter;
+                uint64_t nc = 0, no = 0; b->filtered = deviceFilter; b->depthOnDevice = deviceFilter && ctxDepth;
                 if (!first) { usUpload += (uint64_t)((h1 - h0) * 1e3); usRun += (uint64_t)((h2 - h1) * 1e3); nLater++; }
                 if (deviceFilter && overlapFilter && !first) {                 // the filter thread takes it from here; this thread goes on with the next batch
                     filterIdle();
@@ -481,6 +499,7 @@ int runQueries(Args &a, FILE *log)
     auto formatter = [&]() {
         yaha_session local; local.args = A; local.genome.bases = S->genome.bases; local.genome.nBaseBytes = S->genome.nBaseBytes; local.genome.seqs = S->genome.seqs;
             local.genome.maxROff = S->genome.maxROff;
+        local.depth = depth.get();
         BatchP b;
         while (fmtQ.pop(b)) {
             const double t0 = now(); b->text.clear();
@@ -488,7 +507,7 @@ int runQueries(Args &a, FILE *log)
                 ygpu_filtered_batch fr; memset(&fr, 0, sizeof fr);
                 fr.n_reads = (uint32_t)b->nReads; fr.clump_start = (const uint32_t *)b->clumpStart.p; fr.clumps = (const ygpu_out_clump *)b->clumps.p;
                     fr.ops = (const uint32_t *)b->ops.p; fr.n_clumps = b->nClumps; fr.n_ops = b->nOps;
-                local.reads.swap(b->reads); formatFiltered(&local, &fr, b->text); local.reads.swap(b->reads);
+                local.reads.swap(b->reads); formatFiltered(&local, &fr, b->text, b->depthOnDevice); local.reads.swap(b->reads);
             } else if (!stop && b->nReads) {
                 ygpu_result_batch res; memset(&res, 0, sizeof res);
                 res.n_reads = (uint32_t)b->nReads; res.clump_start = (const uint32_t *)b->clumpStart.p; res.clumps = (const ygpu_clump *)b->clumps.p;
@@ -532,6 +551,16 @@ int runQueries(Args &a, FILE *log)
         (unsigned long long)ticketsIssued.load()); rcAll = 1; }
     // The command line (csrc/main.cpp) leaves right after this function: it sets YAHA_FAST_EXIT and lets the process exit release the device memory and the
     // page-locked buffers in one go, instead of a hipFree per buffer (a second of waiting at the end of every run, measured).  Library users get the orderly path.
+    // the read-depth track: every image's array added to the host's, the bedGraph written after the last alignment
+    if (depth && !stop && rcAll == 0) {
+        std::string derr;
+        for (int k = 0; k < nDev; k++) if (const int c1 = depthCtx[k].load()) {
+            const int rcD = depth->deviceCollect(ctx[c1 - 1], derr);
+            if (rcD != 0) { fprintf(log, "-ocov: collecting the coverage array of device %d failed (%d): %s\n", devs[k], rcD, derr.c_str()); rcAll = 1; }
+        }
+        if (fflush(out) != 0) rcAll = 1;
+        if (rcAll == 0 && !depth->write(A.covFileName.c_str(), S->genome, derr)) { fprintf(log, "%s\n", derr.c_str()); rcAll = 1; }
+    }
     const bool fastExit = getenv("YAHA_FAST_EXIT") != nullptr;
     if (!fastExit) for (int d = ngpu - 1; d >= 0; d--) if (ctx[d]) ygpu_destroy(ctx[d]);     // clones before their parents
     // (the batches -- a million small strings, the page-locked buffers -- go with the process as well: freeing them one by one was 0.3 s)
@@ -544,14 +573,17 @@ int runQueries(Args &a, FILE *log)
         std::string per = "[";
         for (int k = 0; k < nDev; k++) { char t[32]; snprintf(t, sizeof t, "%s%llu", k ? ", " : "", (unsigned long long)devReads[k].load()); per += t; }
         per += "]";
+        char dstat[256] = "";
+        if (depth) snprintf(dstat, sizeof dstat, ", \"depth_bins\": %llu, \"depth_device_records\": %llu, \"depth_host_records\": %llu, \"depth_covered_bases\": %llu",
+            (unsigned long long)depth->nBins, (unsigned long long)depth->devRecords, (unsigned long long)depth->hostRecords, (unsigned long long)depth->coveredBases());
         fprintf(stderr, "[yaha] stats {\"reads\": %llu, \"contexts_up_ms\": %.1f, \"first_batch_written_ms\": %.1f, \"last_batch_written_ms\": %.1f, \"total_ms\": %.1f, "
             "\"steady_reads_per_s\": %.0f, \"cpus\": %d, \"formatters\": %d, \"parsers\": %d, \"gpus\": %d, \"ctx_per_gpu\": %d, \"ctx_left_out\": %d, "
             "\"reads_per_device\": %s, \"context_thread_ms_per_batch\": {\"wait_for_a_batch\": %.2f, \"upload\": %.2f, \"run\": %.2f, \"wait_for_filter_thread\": %.2f, "
-            "\"snapshot\": %.2f}, \"filter_thread_ms_per_batch\": %.2f}\n",
+            "\"snapshot\": %.2f}, \"filter_thread_ms_per_batch\": %.2f%s}\n",
                 (unsigned long long)nWritten, tCtxUp - tEnter, tFirstOut - tEnter, tLastOut - tEnter, now() - tEnter, steady, cpus, nFmt, nParse, nDev, perDev, parked.load(),
                     per.c_str(),
                 usIdle / 1e3 / std::max<uint64_t>(1, nLater), usUpload / 1e3 / std::max<uint64_t>(1, nLater), usRun / 1e3 / std::max<uint64_t>(1, nLater),
-                    usWaitFilter / 1e3 / std::max<uint64_t>(1, nLater), usSnapshot / 1e3 / std::max<uint64_t>(1, nLater), usFilter / 1e3 / std::max<uint64_t>(1, nLater));
+                    usWaitFilter / 1e3 / std::max<uint64_t>(1, nLater), usSnapshot / 1e3 / std::max<uint64_t>(1, nLater), usFilter / 1e3 / std::max<uint64_t>(1, nLater), dstat);
     }
     return rcAll;
 }
@@ -601,6 +633,14 @@ int yaha_session_postfilter_params(yaha_session *s, ygpu_postfilter_params *p)
     p->minNonOverlap = P.minNonOverlap; p->BPCost = P.BPCost; p->maxBPLog = P.maxBPLog; p->FBS = P.FBS; p->FBS_PSLength = P.FBS_PSLength; p->FBS_PSScore = P.FBS_PSScore;
     p->bppVmin = P.bppVmin; p->bppN = P.bppN; p->bppThr = s->pfThr.data(); p->n_seqs = (uint32_t)s->pfSeqStart.size(); p->seq_start = s->pfSeqStart.data();
         p->seq_length = s->pfSeqLen.data();
+    return 0;
+}
+int yaha_session_depth_params(yaha_session *s, ygpu_depth_params *p)
+{
+    if (!s || !p) return YGPU_EINVAL;
+    s->pfSeqStart.clear(); s->pfSeqLen.clear(); for (auto &sq : s->genome.seqs) { s->pfSeqStart.push_back(sq.start); s->pfSeqLen.push_back(sq.length); }
+    p->bin = (uint32_t)s->args.covBin; p->min_mapq = (uint32_t)s->args.covMinQ; p->n_seqs = (uint32_t)s->pfSeqStart.size(); p->seq_start = s->pfSeqStart.data();
+    p->seq_length = s->pfSeqLen.data();
     return 0;
 }
 int yaha_session_emit_filtered(yaha_session *s, const ygpu_filtered_batch *r, const char **text, size_t *len)

@@ -71,6 +71,8 @@ struct Args {
     int maxQueryLength = 32000; bool verbose = false, outputBlast8 = false, outputSAM = true, hardClip = true;
     // extensions of this implementation (not in the reference CLI)
     int batchReads = 0; int device = 0; int gpus = 1; int ctxPerGpu = 3; bool cpuIndex = false; bool devicePostFilter = true;      // batchReads 0: batches of ~16 M bases
+    // read-depth track: -ocov FILE (bedGraph), -covbin B (bases a bin), -covq Q (records below this mapping quality cover nothing)
+    bool haveCov = false, haveCovBin = false, haveCovQ = false; std::string covFileName; int covBin = 100, covMinQ = 0;
     bool query = false, index = true, compress = false, uncompress = false;   // -c / -u: .fa -> .nib2 / .nib2 -> .fasta only (Main.c:284-293, non-user builds of the reference)
 };
 void postProcessArgs(Args &a, bool query);                                  // AlignArgs.c:108-169
@@ -134,6 +136,27 @@ struct Text {
     void grow(size_t need) { size_t c = cap ? cap : (1u << 16); while (c < need) c += c / 2; char *q = (char *)realloc(p, c); if (!q) throw std::bad_alloc(); p = q; cap = c; }
 };
 void printClump(const Args &a, const Genome &g, const Read &r, const OutClump &oc, int primaryCount, Text &out);
+
+// ---- read depth along the reference (-ocov; depth.cpp, ../depth_core.h) -----------------------------------------------------------------------------------
+// The host's coverage array, in the layout the device uses (one routine, depth_core.h): the formatter threads add the records the device did NOT count -- runs
+// whose post-filter stays on the host (-dpf N, -OQC N, YAHA_HOST_OQC=1), the reads the device stage hands back unfiltered, and everything when the library has
+// no device entry points for depth or refuses to enable them -- with relaxed atomics.  At the end of the run the device's arrays (one per index image) are added
+// and the bedGraph is written.  The ygpu_depth_* entry points are looked up weakly: host code links and runs without them (the CPU tier's test doubles).
+struct DepthTrack {
+    std::vector<uint32_t> seqStart, seqLength, binBase; uint64_t nBins = 0; uint32_t bin = 100, minMapq = 0;
+    uint32_t *cov = nullptr;                                              // nBins words, zeroed; relaxed atomic adds
+    uint64_t hostRecords = 0, hostSkipped = 0, hostDropped = 0;           // (atomic adds as well) records the host counted / gated by MAPQ / dropped
+    uint64_t devRecords = 0, devSkipped = 0, devDropped = 0, devHandedBack = 0;
+    DepthTrack() {} DepthTrack(const DepthTrack &) = delete; DepthTrack &operator=(const DepthTrack &) = delete;
+    ~DepthTrack() { free(cov); }
+    bool init(const Genome &g, int binBases, int minQ, std::string &err);
+    void add(const OutClump &oc);                                         // one record printClump was called for
+    static bool deviceEntryPoints();                                      // does this build have ygpu_depth_*?
+    int  deviceEnable(ygpu_ctx *ctx) const;                               // YGPU_ENODEV without the entry points
+    int  deviceCollect(ygpu_ctx *ctx, std::string &err);                  // adds the image's array and statistics to this track
+    uint64_t coveredBases() const;
+    bool write(const char *path, const Genome &g, std::string &err) const;      // bedGraph; path "stdout" = standard output
+};
 }  // namespace yaha
 namespace yoqc { struct Params; }
 namespace yaha {
