@@ -232,6 +232,30 @@ int  ygpu_depth_size(ygpu_ctx *ctx, uint64_t *n_bins);
  * stats (may be NULL): records counted, records skipped (MAPQ), records dropped (two sequences), reads left to the caller (handed back unfiltered). */
 int  ygpu_depth_collect(ygpu_ctx *ctx, uint32_t *bins, uint64_t stats[4]);
 
+/* ---- the evidence track: mismatches, indels and clipped ends along the reference (optional, behind ygpu_postfilter) -------------------------------------------
+ * The third signal of a structural-variant caller beside the split alignments and read depth: where the printed alignments disagree with the reference or stop.
+ * With ygpu_events_enable, every ygpu_postfilter of the context also adds the clumps it returns to ev[bin][channel] (uint32, bin-major, five channels), on the
+ * bin layout of the depth track above, so that a caller can divide by depth.  The contract (yaha_amd/csrc/events_core.h -- one routine for host and device):
+ * channel 0 mismatch: 1 per reference base under an R op; 1 deleted: 1 per reference base under a D op; 2 insertion: 1 per I op, whatever its length, in the bin
+ * of the next reference base the walk reaches (kept inside the record); 3 clip_left: 1 in the bin of the record's first reference base when the printed CIGAR
+ * starts with a clip of at least min_clip bases; 4 clip_right: 1 in the bin of its last reference base when it ends with one.  Hard and soft clips count alike.
+ * As for depth: a clump that spans two sequences is not printed and adds nothing, records with mapQuality < min_mapq add nothing, a count that passes 2^32 - 1
+ * wraps, and reads that come back UNFILTERED (primaryCount == 0xFFFF) are NOT counted: the caller filters them and counts what it prints.
+ * ONE array per index image, 20 * n_bins bytes of device memory (bin 1 on a 3.1 Gbp genome is 62 GB), shared by the image's contexts once each of them has
+ * called ygpu_events_enable with the same parameters -- the first call makes and zeroes it, the others join; other parameters are refused.  When it does not
+ * fit: YGPU_ENOMEM, the sizes in ygpu_last_error.  It lives until the last of those contexts is destroyed; ygpu_park does not touch it.  It does not need the
+ * depth track.  Order: ygpu_set_postfilter, ygpu_events_enable, then batches (ygpu_run, ygpu_postfilter ...), ygpu_events_collect. */
+#define YGPU_EVENTS_CHANNELS 5
+typedef struct ygpu_events_params {
+    uint32_t bin, min_mapq, min_clip, n_seqs;
+    const uint32_t *seq_start, *seq_length;            /* reference sequences in bases, ascending (host memory; copied) */
+} ygpu_events_params;
+int  ygpu_events_enable(ygpu_ctx *ctx, const ygpu_events_params *p);           /* after ygpu_set_postfilter */
+int  ygpu_events_size(ygpu_ctx *ctx, uint64_t *n_bins);
+/* The image's array as it stands, into counts[n_bins * 5], bin-major (may be NULL): waits for every filter stage queued so far on the device, its sibling
+ * contexts' included.  stats (may be NULL): records counted, records skipped (MAPQ), records dropped (two sequences), reads left to the caller. */
+int  ygpu_events_collect(ygpu_ctx *ctx, uint32_t *counts, uint64_t stats[4]);
+
 /* Stage-level entry for tests of the post-filter (as ygpu_dp_batch is for the DP kernels): place a result batch on the device as if ygpu_run had produced it
  * for the reads uploaded last (r->n_reads must equal the uploaded batch's; clump_start / clumps / ops as ygpu_collect returns them).  ygpu_postfilter,
  * ygpu_collect and their siblings then work on it -- so that the device filter can be driven with clump lists no real read produces (hundreds of exact ties,
@@ -336,6 +360,8 @@ int  yaha_session_emit_filtered(yaha_session *s, const ygpu_filtered_batch *r, c
 /* Bin size (-covbin, default 100), least mapping quality (-covq, default 0) and the sequence table for ygpu_depth_enable, from the session's arguments
  * (pointers into the session, valid until it is closed). */
 int  yaha_session_depth_params(yaha_session *s, ygpu_depth_params *p);
+/* The same for ygpu_events_enable: -evbin (default 100), -evq (default 0), -evclip (default 1) and the sequence table (pointers of their own into the session). */
+int  yaha_session_events_params(yaha_session *s, ygpu_events_params *p);
 /* `yaha -g genome.fa [-L k] [-S s] [-H h]`: writes genome.nib2 and genome.X<LL>_<SS>_<HHHHH>S (Main.c:554-628). */
 int  yaha_build_index(int argc, const char *const *argv);
 /* The complete command-line program (index creation or query alignment on the GPU). */

@@ -79,6 +79,13 @@ class DepthParams(C.Structure):
 DEPTH_STATS = ("records_counted", "records_skipped_mapq", "records_dropped_two_sequences", "reads_left_to_host")
 
 
+class EventsParams(C.Structure):
+    _fields_ = [("bin", C.c_uint32), ("min_mapq", C.c_uint32), ("min_clip", C.c_uint32), ("n_seqs", C.c_uint32), ("seq_start", C.c_void_p), ("seq_length", C.c_void_p)]
+
+
+EVENTS_CHANNELS = ("mismatch", "deleted", "insertion", "clip_left", "clip_right")
+
+
 class OutClump(C.Structure):
     _fields_ = [("c", Clump), ("status", C.c_uint8), ("mapQuality", C.c_uint8), ("numSecondaries", C.c_uint16), ("matchedPrimary", C.c_uint16), ("primaryCount", C.c_uint16)]
 
@@ -98,6 +105,7 @@ DP_KERNELS_AUTO, DP_KERNELS_WAVE, DP_KERNELS_LANES, DP_KERNELS_LANES_CAREFUL = 0
 EXPORTS = (
     "ygpu_device_count", "ygpu_init", "ygpu_init_multi", "ygpu_clone", "ygpu_destroy", "ygpu_last_error", "ygpu_memory", "ygpu_park", "ygpu_get_arena_profile", "ygpu_presize", "ygpu_upload", "ygpu_upload_nowait", "ygpu_run", "ygpu_collect", "ygpu_result_size", "ygpu_collect_into", "ygpu_host_alloc", "ygpu_host_free", "ygpu_set_postfilter", "ygpu_postfilter_snapshot", "ygpu_postfilter", "ygpu_postfilter_drop", "ygpu_inject_results", "ygpu_selftest_primitives", "ygpu_trace_volume", "ygpu_filtered_size", "ygpu_collect_filtered", "ygpu_last_timing",
     "ygpu_depth_enable", "ygpu_depth_size", "ygpu_depth_collect", "yaha_session_depth_params",
+    "ygpu_events_enable", "ygpu_events_size", "ygpu_events_collect", "yaha_session_events_params",
     "ygpu_submit", "ygpu_poll", "ygpu_wait", "ygpu_seed_join", "ygpu_chain", "ygpu_dp_batch", "ygpu_dp_batch_ex",
     "yaha_session_open", "yaha_session_close", "yaha_session_error", "yaha_session_params",
     "yaha_session_index_view", "yaha_session_header", "yaha_session_next_batch", "yaha_session_emit", "yaha_session_postfilter_params", "yaha_session_emit_filtered",
@@ -285,6 +293,23 @@ class Context:
         bins = np.zeros(max(1, n.value), dtype=np.uint32); st = (C.c_uint64 * 4)()
         self._check(lib().ygpu_depth_collect(self._h, bins.ctypes.data_as(C.POINTER(C.c_uint32)), st), "ygpu_depth_collect")
         return bins[:n.value], {k: int(st[i]) for i, k in enumerate(DEPTH_STATS)}
+
+    def events_enable(self, session):
+        """The evidence track of the printed clumps behind postfilter() (ygpu_events_enable), with the session's -evbin / -evq / -evclip and sequence table.
+        After set_postfilter(); the contexts of one index image share one array."""
+        p = EventsParams()
+        if lib().yaha_session_events_params(session._h, C.byref(p)) != 0:
+            raise RuntimeError("yaha_session_events_params: " + lib().yaha_session_error(session._h).decode())
+        self._check(lib().ygpu_events_enable(self._h, C.byref(p)), "ygpu_events_enable")
+
+    def events_collect(self):
+        """(evidence array of the context's index image as it stands -- numpy uint32 of shape (n_bins, 5), channels EVENTS_CHANNELS -- and the statistics as a dict)."""
+        import numpy as np
+        n = C.c_uint64()
+        self._check(lib().ygpu_events_size(self._h, C.byref(n)), "ygpu_events_size")
+        ev = np.zeros((max(1, n.value), len(EVENTS_CHANNELS)), dtype=np.uint32); st = (C.c_uint64 * 4)()
+        self._check(lib().ygpu_events_collect(self._h, ev.ctypes.data_as(C.POINTER(C.c_uint32)), st), "ygpu_events_collect")
+        return ev[:n.value], {k: int(st[i]) for i, k in enumerate(DEPTH_STATS)}
 
     def inject_results(self, result):
         """Stage-level test entry: a ResultBatch placed on the device as if ygpu_run had produced it for the uploaded reads."""

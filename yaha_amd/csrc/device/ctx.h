@@ -127,6 +127,18 @@ struct DepthImage {
     ~DepthImage() { (void)hipSetDevice(device); cov.release(); stats.release(); seqStart.release(); seqLength.release(); binBase.release(); }
 };
 
+// The evidence track (-oev; events_stage.h, ../events_core.h): ONE array per index image as well -- five uint32 channels a bin, 20 bytes a bin, on -ocov's bin
+// layout -- with the life cycle of DepthImage: made by the image's first ygpu_events_enable, held by every context that enabled it, untouched by ygpu_park.
+// It keeps a sequence table of its own, so that it does not depend on depth being enabled.
+struct EventsImage {
+    int device = 0;
+    DevBuf ev, stats, seqStart, seqLength, binBase;
+    uint64_t nBins = 0;
+    uint32_t bin = 0, minMapq = 0, minClip = 0;
+    std::vector<uint32_t> hSeqStart, hSeqLength;                  // what it was enabled with (a second enable must agree)
+    ~EventsImage() { (void)hipSetDevice(device); ev.release(); stats.release(); seqStart.release(); seqLength.release(); binBase.release(); }
+};
+
 struct ygpu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -201,6 +213,7 @@ struct ygpu_ctx {
     unsigned long long snapHits = 0, snapFrags = 0, snapRegions = 0;
     DevBuf oqCs, oqCl, oqOpsIn, oqSeeds, oqQlen;
     std::shared_ptr<DepthImage> depth;           // set by ygpu_depth_enable: the post-filter then feeds the image's coverage array
+    std::shared_ptr<EventsImage> events;         // set by ygpu_events_enable: the post-filter then feeds the image's evidence array
     // stage state
     uint32_t hOutCounts[2] = {0, 0}, hOutEf = 0;
     bool hOutValid = false;

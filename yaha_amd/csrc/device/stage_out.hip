@@ -1,9 +1,11 @@
 // stage_out.hip -- what leaves the device: the batch's results as ygpu_run left them (ygpu_collect*), and the post-filter stage (postFilterBySimilarity,
 // GraphPath.cpp:897-1086, Query.c:450) on a snapshot of them -- oqc_stage.h -- with its own stream, wait slot and look-back words (PfSide); behind it, when
-// ygpu_depth_enable asked for it, the read-depth track of the printed clumps (depth_stage.h).
+// ygpu_depth_enable asked for it, the read-depth track of the printed clumps (depth_stage.h), and when ygpu_events_enable did, their evidence track
+// (events_stage.h).
 #include "ctx.h"
 #include "oqc_stage.h"
 #include "depth_stage.h"
+#include "events_stage.h"
 #include <map>
 
 extern "C" {
@@ -190,6 +192,22 @@ static int postfilterBody(ygpu_ctx *full)
     ENSURE(full->oqFClumps, sizeof(ygpu_out_clump) * ((uint64_t)tot[0] + 1)); ENSURE(full->oqFOps, 4ull * ((uint64_t)tot[1] + 1));
     KL(k_oqc_gather, dim3(gridFor((uint64_t)n * 64, 256)), dim3(256), 0, ctx->stream, A, full->oqOutStart.as<uint32_t>(), full->oqOpsStart.as<uint32_t>(),
         full->oqFClumps.as<ygpu_out_clump>(), full->oqFOps.as<uint32_t>());
+    // the evidence track (-oev): mismatches, deleted bases, insertions and clipped ends of the clumps just gathered, a wave each, on this stage's stream; the
+    // wave finds its clump's read -- the query length of the right clip -- in oqOutStart.  (YGPU_EVENTS_DIRECT: every op's atomics without the combining in the
+    // wave, for measurements; read at every call.)
+    if (full->events && tot[0]) {
+        EventsImage &EI = *full->events; EventsArgs E;
+        E.L.seqStart = EI.seqStart.as<uint32_t>(); E.L.seqLength = EI.seqLength.as<uint32_t>(); E.L.binBase = EI.binBase.as<uint32_t>();
+        E.L.nSeqs = (uint32_t)EI.hSeqStart.size(); E.L.bin = EI.bin; E.L.minMapq = EI.minMapq; E.minClip = EI.minClip;
+        E.ev = EI.ev.as<uint32_t>(); E.nBins = (uint32_t)EI.nBins; E.stats = EI.stats.as<unsigned long long>();
+        const dim3 grid(gridFor((uint64_t)tot[0] * 64, 256));
+        if (EI.bin > 1 && getenv("YGPU_EVENTS_DIRECT") == nullptr)
+            KL(k_event_clumps<true>, grid, dim3(256), 0, ctx->stream, E, full->oqFClumps.as<ygpu_out_clump>(), full->oqFOps.as<uint32_t>(), full->oqOutStart.as<uint32_t>(),
+                full->oqQlen.as<uint32_t>(), n, tot[0]);
+        else
+            KL(k_event_clumps<false>, grid, dim3(256), 0, ctx->stream, E, full->oqFClumps.as<ygpu_out_clump>(), full->oqFOps.as<uint32_t>(), full->oqOutStart.as<uint32_t>(),
+                full->oqQlen.as<uint32_t>(), n, tot[0]);
+    }
     // read depth (-ocov): the clumps just gathered are the ones that get printed -- a wave each adds what it covers to the image's array, on this stage's stream
     if (full->depth && tot[0]) {
         DepthImage &DI = *full->depth; DepthArgs D;
@@ -270,6 +288,66 @@ int ygpu_depth_collect(ygpu_ctx *ctx, uint32_t *bins, uint64_t stats[4])
     DepthImage &DI = *ctx->depth;
     if (bins) HIPCHK(hipMemcpy(bins, DI.cov.p, 4ull * DI.nBins, hipMemcpyDeviceToHost));
     if (stats) { unsigned long long h[4]; HIPCHK(hipMemcpy(h, DI.stats.p, sizeof h, hipMemcpyDeviceToHost)); for (int k = 0; k < 4; k++) stats[k] = h[k]; }
+    return 0;
+}
+// ---- the evidence track (events_stage.h; the contract is in ../events_core.h) -----------------------------------------------------------------------------
+// the arrays of this process by index image, as the coverage arrays above
+static std::mutex gEventsMu;
+static std::map<std::pair<int, const void *>, std::weak_ptr<EventsImage>> gEventsImages;
+int ygpu_events_enable(ygpu_ctx *ctx, const ygpu_events_params *p)
+{
+    if (!ctx || !ctx->stream || !p) return YGPU_EINVAL;
+    if (!ctx->oqSet) { ctx->err = "ygpu_events_enable: ygpu_set_postfilter has not been called on this context (the events are counted behind the post-filter)";
+        return YGPU_EINVAL; }
+    if (p->bin < 1 || p->min_clip < 1 || !p->n_seqs || !p->seq_start || !p->seq_length) { ctx->err = "ygpu_events_enable: bad bin size, clip length or sequence table";
+        return YGPU_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    std::lock_guard<std::mutex> lk(gEventsMu);
+    const std::pair<int, const void *> key(ctx->device, ctx->dBases.p);
+    if (std::shared_ptr<EventsImage> have = gEventsImages[key].lock()) {    // a sibling enabled it: the same array, if the same track is asked for
+        if (have->bin != p->bin || have->minMapq != p->min_mapq || have->minClip != p->min_clip || have->hSeqStart.size() != p->n_seqs
+            || memcmp(have->hSeqStart.data(), p->seq_start, 4ull * p->n_seqs) != 0 || memcmp(have->hSeqLength.data(), p->seq_length, 4ull * p->n_seqs) != 0) {
+            ctx->err = "ygpu_events_enable: the image's evidence array was enabled with other parameters"; return YGPU_EINVAL; }
+        ctx->events = have; return 0;
+    }
+    std::shared_ptr<EventsImage> EI(new EventsImage); EI->device = ctx->device; EI->bin = p->bin; EI->minMapq = p->min_mapq; EI->minClip = p->min_clip;
+    EI->hSeqStart.assign(p->seq_start, p->seq_start + p->n_seqs); EI->hSeqLength.assign(p->seq_length, p->seq_length + p->n_seqs);
+    std::vector<uint32_t> binBase(p->n_seqs + 1);
+    if (!ydepth::layoutBins(p->seq_length, p->n_seqs, p->bin, binBase.data(), &EI->nBins) || EI->nBins == 0) { ctx->err = "ygpu_events_enable: the bins do not fit 32 bits";
+        return YGPU_EINVAL; }
+    const uint64_t bytes = 4ull * yevents::NCH * EI->nBins;
+    if (EI->ev.ensureExact(bytes)) {
+        (void)hipGetLastError(); size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) != hipSuccess) { fb = 0; (void)hipGetLastError(); }
+        char m[256]; snprintf(m, sizeof m, "ygpu_events_enable: no room on device %d for the evidence array: %.2f GB for %llu bins of %u bases (20 bytes a bin), %.2f GB free "
+            "(a larger -evbin needs less)", ctx->device, bytes / 1e9, (unsigned long long)EI->nBins, p->bin, fb / 1e9);
+        ctx->err = m; return YGPU_ENOMEM;
+    }
+    if (EI->stats.ensure(64) || EI->seqStart.ensure(4ull * p->n_seqs) || EI->seqLength.ensure(4ull * p->n_seqs) || EI->binBase.ensure(4ull * (p->n_seqs + 1))) {
+        (void)hipGetLastError(); ctx->err = "ygpu_events_enable: hipMalloc failed"; return YGPU_ENOMEM; }
+    HIPCHK(hipMemsetAsync(EI->ev.p, 0, bytes, ctx->stream)); HIPCHK(hipMemsetAsync(EI->stats.p, 0, 64, ctx->stream));
+    HIPCHK(hipMemcpyAsync(EI->seqStart.p, p->seq_start, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(EI->seqLength.p, p->seq_length, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(EI->binBase.p, binBase.data(), 4ull * (p->n_seqs + 1), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(streamSync(ctx));
+    gEventsImages[key] = EI; ctx->events = EI;
+    return 0;
+}
+int ygpu_events_size(ygpu_ctx *ctx, uint64_t *n_bins)
+{
+    if (!ctx || !n_bins) return YGPU_EINVAL;
+    if (!ctx->events) { ctx->err = "ygpu_events_size: ygpu_events_enable has not been called on this context"; return YGPU_EINVAL; }
+    *n_bins = ctx->events->nBins; return 0;
+}
+// The image's array as it stands: every filter stage queued on the device so far -- this context's and its siblings' -- has finished when the copy is taken.
+int ygpu_events_collect(ygpu_ctx *ctx, uint32_t *counts, uint64_t stats[4])
+{
+    if (!ctx || !ctx->stream) return YGPU_EINVAL;
+    if (!ctx->events) { ctx->err = "ygpu_events_collect: ygpu_events_enable has not been called on this context"; return YGPU_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipDeviceSynchronize());
+    EventsImage &EI = *ctx->events;
+    if (counts) HIPCHK(hipMemcpy(counts, EI.ev.p, 4ull * yevents::NCH * EI.nBins, hipMemcpyDeviceToHost));
+    if (stats) { unsigned long long h[4]; HIPCHK(hipMemcpy(h, EI.stats.p, sizeof h, hipMemcpyDeviceToHost)); for (int k = 0; k < 4; k++) stats[k] = h[k]; }
     return 0;
 }
 int ygpu_inject_results(ygpu_ctx *ctx, const ygpu_result_batch *r)

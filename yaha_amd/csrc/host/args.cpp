@@ -2,7 +2,8 @@
 // file-name derivation as the reference CLI (Main.c:187-565, AlignArgs.c:27-169) so that
 // `yaha -g genome.fa` / `yaha -x index -q reads ...` keep working unchanged.  Extra options of this
 // implementation: -gpus N (shard batches over N devices), -ctx M (contexts per device), -device D, -batch N (reads per device batch),
-// -ocov FILE / -covbin B / -covq Q (read depth of the printed records as bedGraph).
+// -ocov FILE / -covbin B / -covq Q (read depth of the printed records as bedGraph), -oev FILE / -evbin B / -evq Q / -evclip N (their mismatches, indels and
+// clipped ends per bin).
 #include "yaha_host.h"
 #include <cstring>
 #include <cstdlib>
@@ -27,7 +28,12 @@ static void usage(FILE *o)
           "  depth   : [-ocov depthFile|stdout] [-covbin basesPerBin (100)] [-covq minMapQ (0)]\n"
           "       read depth of the printed records along the reference (bases under M of the CIGAR) as bedGraph, written after the last alignment;\n"
           "       accumulated on the device behind its post-filter: 4 bytes a bin of device memory per GPU -- -covbin 1 on a 3.1 Gbp genome is 12.4 GB beside the\n"
-          "       contexts' arenas; when that does not fit the run stops before the first batch and says so (use a larger bin or a smaller -ctx).\n", o);
+          "       contexts' arenas; when that does not fit the run stops before the first batch and says so (use a larger bin or a smaller -ctx).\n"
+          "  events  : [-oev eventsFile|stdout] [-evbin basesPerBin (100)] [-evq minMapQ (0)] [-evclip minClippedBases (1)]\n"
+          "       where the printed records disagree with the reference or stop, per bin (the bins of -ocov): mismatched bases, deleted bases, insertions,\n"
+          "       records clipped by at least -evclip bases at their left / right end; tab-separated with a header line, bins without events left out, written\n"
+          "       after the last alignment.  Accumulated on the device like the depth: 20 bytes a bin of device memory per GPU -- -evbin 1 on a 3.1 Gbp genome\n"
+          "       is 62 GB; when that does not fit the run stops before the first batch and says so (use a larger bin).\n", o);
 }
 
 static bool parseBool(const char *s, const char *key, bool &out)
@@ -107,6 +113,13 @@ int parseArgs(int argc, char **argv, Args &a)
         else if (is("-covbin")) { if (!parseInt(val(), "-covbin", a.covBin)) return 3; a.haveCovBin = true;
             if (a.covBin < 1) { fprintf(stderr, "-covbin must be at least 1 (bases per bin).\n\n"); usage(stderr); return 3; } }
         else if (is("-covq")) { if (!parseInt(val(), "-covq", a.covMinQ)) return 3; a.haveCovQ = true; }
+        else if (is("-oev")) { const char *v = val(); a.evFileName = (!strcmp(v, "-stdout")) ? "stdout" : v; a.haveEv = true;
+            if (a.evFileName.empty()) { fprintf(stderr, "-oev needs a file name.\n\n"); usage(stderr); return 3; } }
+        else if (is("-evbin")) { if (!parseInt(val(), "-evbin", a.evBin)) return 3; a.haveEvBin = true;
+            if (a.evBin < 1) { fprintf(stderr, "-evbin must be at least 1 (bases per bin).\n\n"); usage(stderr); return 3; } }
+        else if (is("-evq")) { if (!parseInt(val(), "-evq", a.evMinQ)) return 3; a.haveEvQ = true; }
+        else if (is("-evclip")) { if (!parseInt(val(), "-evclip", a.evMinClip)) return 3; a.haveEvClip = true;
+            if (a.evMinClip < 1) { fprintf(stderr, "-evclip must be at least 1 (clipped bases).\n\n"); usage(stderr); return 3; } }
         else { fprintf(stderr, "%s is not a valid option.\n\n", k); usage(stderr); return 2; }
     }
     a.query = query; a.index = index && !query;
@@ -115,6 +128,13 @@ int parseArgs(int argc, char **argv, Args &a)
     if (a.haveCov && !query) { fprintf(stderr, "-ocov is an output of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return 3; }
     if (a.haveCov && a.covFileName == "stdout" && (!a.haveO || a.ofileName == "stdout")) {
         fprintf(stderr, "-ocov stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
+    // the evidence track: the same rules, and the two tracks cannot share standard output either
+    if (!a.haveEv && (a.haveEvBin || a.haveEvQ || a.haveEvClip)) { fprintf(stderr, "-evbin, -evq and -evclip need -oev.\n\n"); usage(stderr); return 3; }
+    if (a.haveEv && !query) { fprintf(stderr, "-oev is an output of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return 3; }
+    if (a.haveEv && a.evFileName == "stdout" && (!a.haveO || a.ofileName == "stdout")) {
+        fprintf(stderr, "-oev stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
+    if (a.haveEv && a.haveCov && a.evFileName == "stdout" && a.covFileName == "stdout") {
+        fprintf(stderr, "-oev stdout: the depth track (-ocov) already goes to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
     if ((a.compress || a.uncompress) && !query) {                                                  // Main.c:472-533: -c wants a FASTA genome, -u a .nib2
         if (!a.haveG) { fprintf(stderr, "Genome file specification (-g) is required for index creation.\n\n"); usage(stderr); return 2; }
         size_t dot = a.gfileName.rfind('.'); const std::string ext = dot == std::string::npos ? "" : a.gfileName.substr(dot);
@@ -181,6 +201,7 @@ std::string samHeader(const Args &a, const Genome &g)                   // outpu
         if (a.FBS) { snprintf(buf, sizeof buf, " -FBS Y -PRL %4.2f -PSS %4.2f", a.FBS_PSLength, a.FBS_PSScore); h += buf; } else h += " -FBS N";
     } else h += " -OQC N";
     if (a.haveCov) { snprintf(buf, sizeof buf, " -covbin %d -covq %d", a.covBin, a.covMinQ); h += " -ocov " + a.covFileName + buf; }
+    if (a.haveEv) { snprintf(buf, sizeof buf, " -evbin %d -evq %d -evclip %d", a.evBin, a.evMinQ, a.evMinClip); h += " -oev " + a.evFileName + buf; }
     h += "\n";
     return h;
 }

@@ -22,10 +22,12 @@ using namespace yaha;
 
 struct yaha_session {
     Args args; Genome genome; IndexFile index; ReadReader reader; std::string err, header; Text text;
+    std::vector<uint32_t> evSeqStart, evSeqLen;                      // what yaha_session_events_params points into
     std::vector<uint32_t> pfThr, pfSeqStart, pfSeqLen;               // what yaha_session_postfilter_params points into
     std::vector<Read> reads; std::vector<uint8_t> codes; std::vector<uint64_t> offsets;
     bool readerOpen = false;
     DepthTrack *depth = nullptr;                                     // -ocov (the command line): the formatters add the records the device did not count
+    EventsTrack *events = nullptr;                                   // -oev: the same for the evidence track
 };
 
 namespace yaha {
@@ -128,12 +130,12 @@ static void formatRange(const yaha_session *s, const ygpu_result_batch *r, uint3
     for (uint32_t i = i0; i < i1; i++) {
         uint32_t c0 = r->clump_start[i], c1 = r->clump_start[i + 1]; int primaryCount = 0;
         postFilter(a, s->genome, s->reads[i], r->clumps + c0, c1 - c0, r->ops, oc, primaryCount);
-        for (auto &o : oc) { printClump(a, s->genome, s->reads[i], o, primaryCount, text); if (s->depth) s->depth->add(o); }
+        for (auto &o : oc) { printClump(a, s->genome, s->reads[i], o, primaryCount, text); if (s->depth) s->depth->add(o); if (s->events) s->events->add(o, s->reads[i].len()); }
     }
 }
 // SAM text of a batch whose post-filter ran on the device (ygpu_postfilter): the clumps arrive in print order with the filter's fields set
-// (depthOnDevice: the device stage counted the batch's read depth as well -- all but the reads it handed back unfiltered)
-static void formatFiltered(const yaha_session *s, const ygpu_filtered_batch *r, Text &text, bool depthOnDevice = false)
+// (depthOnDevice / eventsOnDevice: the device stage counted the batch's read depth / evidence track as well -- all but the reads it handed back unfiltered)
+static void formatFiltered(const yaha_session *s, const ygpu_filtered_batch *r, Text &text, bool depthOnDevice = false, bool eventsOnDevice = false)
 {
     const Args &a = s->args; text.clear();
     std::vector<ygpu_clump> raw; std::vector<OutClump> oc;
@@ -144,7 +146,8 @@ static void formatFiltered(const yaha_session *s, const ygpu_filtered_batch *r, 
             raw.resize(k1 - k0); for (uint32_t k = k0; k < k1; k++) raw[k - k0] = r->clumps[k].c;
             int primaryCount = 0;
             postFilter(a, s->genome, s->reads[i], raw.data(), k1 - k0, r->ops, oc, primaryCount);
-            for (auto &o : oc) { printClump(a, s->genome, s->reads[i], o, primaryCount, text); if (s->depth) s->depth->add(o); }
+            for (auto &o : oc) { printClump(a, s->genome, s->reads[i], o, primaryCount, text); if (s->depth) s->depth->add(o);
+                if (s->events) s->events->add(o, s->reads[i].len()); }
             continue;
         }
         for (uint32_t k = k0; k < k1; k++) {
@@ -153,6 +156,7 @@ static void formatFiltered(const yaha_session *s, const ygpu_filtered_batch *r, 
                 o.matchedPrimary = f.matchedPrimary;
             printClump(a, s->genome, s->reads[i], o, (int)f.primaryCount, text);
             if (s->depth && !depthOnDevice) s->depth->add(o);
+            if (s->events && !eventsOnDevice) s->events->add(o, s->reads[i].len());
         }
     }
 }
@@ -215,6 +219,9 @@ int runQueries(Args &a, FILE *log)
     // -ocov: the host's coverage array (depth.cpp); the device stage behind the post-filter feeds one of its own per index image, merged at the end
     std::unique_ptr<DepthTrack> depth;
     if (A.haveCov) { depth.reset(new DepthTrack); if (!depth->init(S->genome, A.covBin, A.covMinQ, S->err)) { fprintf(log, "%s\n", S->err.c_str()); return 1; } }
+    // -oev: the same for the evidence track (events.cpp)
+    std::unique_ptr<EventsTrack> events;
+    if (A.haveEv) { events.reset(new EventsTrack); if (!events->init(S->genome, A.evBin, A.evMinQ, A.evMinClip, S->err)) { fprintf(log, "%s\n", S->err.c_str()); return 1; } }
     setvbuf(out, nullptr, _IONBF, 0);                                       // whole batches are written with one call each
     if (fputs(S->header.c_str(), out) < 0) { fprintf(log, "Failure writing the output file.\n"); return 1; }
     ygpu_params P; paramsFromArgs(A, P);
@@ -250,7 +257,8 @@ int runQueries(Args &a, FILE *log)
         }
     };
     struct Batch { uint64_t ticket = 0; std::vector<Span> spans; std::vector<Read> reads; size_t nReads = 0; std::vector<uint8_t> codes; std::vector<uint64_t> offsets;
-                   ResBuf clumpStart, ops, clumps; uint64_t nClumps = 0, nOps = 0; bool filtered = false, depthOnDevice = false; Text text; double tRead = 0, tDev = 0, tFmt = 0; };
+                   ResBuf clumpStart, ops, clumps; uint64_t nClumps = 0, nOps = 0; bool filtered = false, depthOnDevice = false, eventsOnDevice = false; Text text;
+                   double tRead = 0, tDev = 0, tFmt = 0; };
     typedef std::unique_ptr<Batch> BatchP;
     struct Pool { std::mutex mu; std::vector<BatchP> free; BatchP get() { { std::lock_guard<std::mutex> lk(mu); if (!free.empty()) { BatchP b = std::move(free.back());
         free.pop_back(); return b; } } return BatchP(new Batch); }
@@ -325,6 +333,9 @@ int runQueries(Args &a, FILE *log)
     // that feeds it.  Without the entry points (a build without them) or when the stage is refused, the formatters count everything.
     const bool depthDevice = depth && deviceFilter && DepthTrack::deviceEntryPoints() && getenv("YAHA_HOST_DEPTH") == nullptr;
     std::vector<std::atomic<int>> depthCtx(nDev); for (auto &x : depthCtx) x = 0;
+    // the evidence track on the device: the same arrangement (YAHA_HOST_EVENTS: the formatters count everything)
+    const bool eventsDevice = events && deviceFilter && EventsTrack::deviceEntryPoints() && getenv("YAHA_HOST_EVENTS") == nullptr;
+    std::vector<std::atomic<int>> eventsCtx(nDev); for (auto &x : eventsCtx) x = 0;
     std::vector<std::atomic<uint64_t>> devReads(nDev); for (auto &x : devReads) x = 0;       // reads each device took (the stats line: do all devices pull their weight?)
     // where a context thread's time goes, batches after a context's first (the stats line; microseconds): upload, run, waiting for the filter thread, snapshot; and the filter
     // thread's post-filter + collect
@@ -359,6 +370,12 @@ int runQueries(Args &a, FILE *log)
             // device is full; a larger -covbin is the way out).  Any other refusal: this context's records are counted by the formatters.
             if (rcD == YGPU_ENOMEM) { char m[640]; snprintf(m, sizeof m, "-ocov: %s", ygpu_last_error(ctx[d])); fail(m); }
             else if (rcD == 0) { ctxDepth = true; int none = 0; depthCtx[d / perDev].compare_exchange_strong(none, d + 1); }
+        }
+        bool ctxEvents = false;
+        if (rc0 == 0 && eventsDevice) {                                        // (the same rules: no room stops the run before its first batch)
+            const int rcE = events->deviceEnable(ctx[d]);
+            if (rcE == YGPU_ENOMEM) { char m[640]; snprintf(m, sizeof m, "-oev: %s", ygpu_last_error(ctx[d])); fail(m); }
+            else if (rcE == 0) { ctxEvents = true; int none = 0; eventsCtx[d / perDev].compare_exchange_strong(none, d + 1); }
         }
         if (rc0 != 0) { char m[512];
             snprintf(m, sizeof m, "ygpu_init(device %d) failed: %d %s", dev, rc0, ctx[d] ? ygpu_last_error(ctx[d]) : (d == leadCtx ? "" : "(the device's first context failed)"));
@@ -452,7 +469,7 @@ int runQueries(Args &a, FILE *log)
                 // (the batch lives until it is printed: no wait for its bytes here)
                 int rc = ygpu_upload_nowait(ctx[d], &rb); const double h1 = now(); if (rc == 0) rc = ygpu_run(ctx[d]); if (rc != 0) return rc;
                 const double h2 = now();
-                uint64_t nc = 0, no = 0; b->filtered = deviceFilter; b->depthOnDevice = deviceFilter && ctxDepth;
+                uint64_t nc = 0, no = 0; b->filtered = deviceFilter; b->depthOnDevice = deviceFilter && ctxDepth; b->eventsOnDevice = deviceFilter && ctxEvents;
                 if (!first) { usUpload += (uint64_t)((h1 - h0) * 1e3); usRun += (uint64_t)((h2 - h1) * 1e3); nLater++; }
                 if (deviceFilter && overlapFilter && !first) {                 // the filter thread takes it from here; this thread goes on with the next batch
                     filterIdle();
@@ -499,7 +516,7 @@ int runQueries(Args &a, FILE *log)
     auto formatter = [&]() {
         yaha_session local; local.args = A; local.genome.bases = S->genome.bases; local.genome.nBaseBytes = S->genome.nBaseBytes; local.genome.seqs = S->genome.seqs;
             local.genome.maxROff = S->genome.maxROff;
-        local.depth = depth.get();
+        local.depth = depth.get(); local.events = events.get();
         BatchP b;
         while (fmtQ.pop(b)) {
             const double t0 = now(); b->text.clear();
@@ -507,7 +524,7 @@ int runQueries(Args &a, FILE *log)
                 ygpu_filtered_batch fr; memset(&fr, 0, sizeof fr);
                 fr.n_reads = (uint32_t)b->nReads; fr.clump_start = (const uint32_t *)b->clumpStart.p; fr.clumps = (const ygpu_out_clump *)b->clumps.p;
                     fr.ops = (const uint32_t *)b->ops.p; fr.n_clumps = b->nClumps; fr.n_ops = b->nOps;
-                local.reads.swap(b->reads); formatFiltered(&local, &fr, b->text, b->depthOnDevice); local.reads.swap(b->reads);
+                local.reads.swap(b->reads); formatFiltered(&local, &fr, b->text, b->depthOnDevice, b->eventsOnDevice); local.reads.swap(b->reads);
             } else if (!stop && b->nReads) {
                 ygpu_result_batch res; memset(&res, 0, sizeof res);
                 res.n_reads = (uint32_t)b->nReads; res.clump_start = (const uint32_t *)b->clumpStart.p; res.clumps = (const ygpu_clump *)b->clumps.p;
@@ -561,6 +578,16 @@ int runQueries(Args &a, FILE *log)
         if (fflush(out) != 0) rcAll = 1;
         if (rcAll == 0 && !depth->write(A.covFileName.c_str(), S->genome, derr)) { fprintf(log, "%s\n", derr.c_str()); rcAll = 1; }
     }
+    // the evidence track: the same, after the depth track
+    if (events && !stop && rcAll == 0) {
+        std::string eerr;
+        for (int k = 0; k < nDev; k++) if (const int c1 = eventsCtx[k].load()) {
+            const int rcE = events->deviceCollect(ctx[c1 - 1], eerr);
+            if (rcE != 0) { fprintf(log, "-oev: collecting the evidence array of device %d failed (%d): %s\n", devs[k], rcE, eerr.c_str()); rcAll = 1; }
+        }
+        if (fflush(out) != 0) rcAll = 1;
+        if (rcAll == 0 && !events->write(A.evFileName.c_str(), S->genome, eerr)) { fprintf(log, "%s\n", eerr.c_str()); rcAll = 1; }
+    }
     const bool fastExit = getenv("YAHA_FAST_EXIT") != nullptr;
     if (!fastExit) for (int d = ngpu - 1; d >= 0; d--) if (ctx[d]) ygpu_destroy(ctx[d]);     // clones before their parents
     // (the batches -- a million small strings, the page-locked buffers -- go with the process as well: freeing them one by one was 0.3 s)
@@ -573,9 +600,12 @@ int runQueries(Args &a, FILE *log)
         std::string per = "[";
         for (int k = 0; k < nDev; k++) { char t[32]; snprintf(t, sizeof t, "%s%llu", k ? ", " : "", (unsigned long long)devReads[k].load()); per += t; }
         per += "]";
-        char dstat[256] = "";
+        char dstat[512] = "";
         if (depth) snprintf(dstat, sizeof dstat, ", \"depth_bins\": %llu, \"depth_device_records\": %llu, \"depth_host_records\": %llu, \"depth_covered_bases\": %llu",
             (unsigned long long)depth->nBins, (unsigned long long)depth->devRecords, (unsigned long long)depth->hostRecords, (unsigned long long)depth->coveredBases());
+        if (events) { const size_t at = strlen(dstat);
+            snprintf(dstat + at, sizeof dstat - at, ", \"events_bins\": %llu, \"events_device_records\": %llu, \"events_host_records\": %llu, \"events_counted\": %llu",
+                (unsigned long long)events->nBins, (unsigned long long)events->devRecords, (unsigned long long)events->hostRecords, (unsigned long long)events->counted()); }
         fprintf(stderr, "[yaha] stats {\"reads\": %llu, \"contexts_up_ms\": %.1f, \"first_batch_written_ms\": %.1f, \"last_batch_written_ms\": %.1f, \"total_ms\": %.1f, "
             "\"steady_reads_per_s\": %.0f, \"cpus\": %d, \"formatters\": %d, \"parsers\": %d, \"gpus\": %d, \"ctx_per_gpu\": %d, \"ctx_left_out\": %d, "
             "\"reads_per_device\": %s, \"context_thread_ms_per_batch\": {\"wait_for_a_batch\": %.2f, \"upload\": %.2f, \"run\": %.2f, \"wait_for_filter_thread\": %.2f, "
@@ -641,6 +671,14 @@ int yaha_session_depth_params(yaha_session *s, ygpu_depth_params *p)
     s->pfSeqStart.clear(); s->pfSeqLen.clear(); for (auto &sq : s->genome.seqs) { s->pfSeqStart.push_back(sq.start); s->pfSeqLen.push_back(sq.length); }
     p->bin = (uint32_t)s->args.covBin; p->min_mapq = (uint32_t)s->args.covMinQ; p->n_seqs = (uint32_t)s->pfSeqStart.size(); p->seq_start = s->pfSeqStart.data();
     p->seq_length = s->pfSeqLen.data();
+    return 0;
+}
+int yaha_session_events_params(yaha_session *s, ygpu_events_params *p)
+{
+    if (!s || !p) return YGPU_EINVAL;
+    s->evSeqStart.clear(); s->evSeqLen.clear(); for (auto &sq : s->genome.seqs) { s->evSeqStart.push_back(sq.start); s->evSeqLen.push_back(sq.length); }
+    p->bin = (uint32_t)s->args.evBin; p->min_mapq = (uint32_t)s->args.evMinQ; p->min_clip = (uint32_t)s->args.evMinClip; p->n_seqs = (uint32_t)s->evSeqStart.size();
+        p->seq_start = s->evSeqStart.data(); p->seq_length = s->evSeqLen.data();
     return 0;
 }
 int yaha_session_emit_filtered(yaha_session *s, const ygpu_filtered_batch *r, const char **text, size_t *len)

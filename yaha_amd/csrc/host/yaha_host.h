@@ -73,6 +73,8 @@ struct Args {
     int batchReads = 0; int device = 0; int gpus = 1; int ctxPerGpu = 3; bool cpuIndex = false; bool devicePostFilter = true;      // batchReads 0: batches of ~16 M bases
     // read-depth track: -ocov FILE (bedGraph), -covbin B (bases a bin), -covq Q (records below this mapping quality cover nothing)
     bool haveCov = false, haveCovBin = false, haveCovQ = false; std::string covFileName; int covBin = 100, covMinQ = 0;
+    // evidence track: -oev FILE (mismatch / deleted / insertion / clipped-end counts per bin), -evbin B, -evq Q, -evclip N (a clip counts from N bases on)
+    bool haveEv = false, haveEvBin = false, haveEvQ = false, haveEvClip = false; std::string evFileName; int evBin = 100, evMinQ = 0, evMinClip = 1;
     bool query = false, index = true, compress = false, uncompress = false;   // -c / -u: .fa -> .nib2 / .nib2 -> .fasta only (Main.c:284-293, non-user builds of the reference)
 };
 void postProcessArgs(Args &a, bool query);                                  // AlignArgs.c:108-169
@@ -156,6 +158,26 @@ struct DepthTrack {
     int  deviceCollect(ygpu_ctx *ctx, std::string &err);                  // adds the image's array and statistics to this track
     uint64_t coveredBases() const;
     bool write(const char *path, const Genome &g, std::string &err) const;      // bedGraph; path "stdout" = standard output
+};
+
+// ---- the evidence track (-oev; events.cpp, ../events_core.h) ----------------------------------------------------------------------------------------------
+// The host's array of the track -- mismatched bases, deleted bases, insertions, clipped ends left and right: five uint32 a bin, bin-major, on the bins of the
+// depth track -- with DepthTrack's division of labour: the formatter threads add the records the device did NOT count (relaxed atomics), the device's arrays
+// (one per index image) are added at the end of the run and the file is written after the last alignment.  The ygpu_events_* entry points are looked up weakly.
+struct EventsTrack {
+    std::vector<uint32_t> seqStart, seqLength, binBase; uint64_t nBins = 0; uint32_t bin = 100, minMapq = 0, minClip = 1;
+    uint32_t *ev = nullptr;                                               // nBins * 5 words, zeroed; relaxed atomic adds
+    uint64_t hostRecords = 0, hostSkipped = 0, hostDropped = 0;           // (atomic adds as well) records the host counted / gated by MAPQ / dropped
+    uint64_t devRecords = 0, devSkipped = 0, devDropped = 0, devHandedBack = 0;
+    EventsTrack() {} EventsTrack(const EventsTrack &) = delete; EventsTrack &operator=(const EventsTrack &) = delete;
+    ~EventsTrack() { free(ev); }
+    bool init(const Genome &g, int binBases, int minQ, int minClipBases, std::string &err);
+    void add(const OutClump &oc, int qlen);                               // one record printClump was called for, and its read's length
+    static bool deviceEntryPoints();                                      // does this build have ygpu_events_*?
+    int  deviceEnable(ygpu_ctx *ctx) const;                               // YGPU_ENODEV without the entry points
+    int  deviceCollect(ygpu_ctx *ctx, std::string &err);                  // adds the image's array and statistics to this track
+    uint64_t counted() const;                                             // the sum over all bins and channels
+    bool write(const char *path, const Genome &g, std::string &err) const;      // path "stdout" = standard output
 };
 }  // namespace yaha
 namespace yoqc { struct Params; }
