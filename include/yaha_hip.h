@@ -256,6 +256,39 @@ int  ygpu_events_size(ygpu_ctx *ctx, uint64_t *n_bins);
  * contexts' included.  stats (may be NULL): records counted, records skipped (MAPQ), records dropped (two sequences), reads left to the caller. */
 int  ygpu_events_collect(ygpu_ctx *ctx, uint32_t *counts, uint64_t stats[4]);
 
+/* ---- split-read breakpoint calls: where the printed alignments of a read join (optional, behind ygpu_postfilter) ----------------------------------------------
+ * The primary signal of a structural-variant caller.  With ygpu_junctions_enable, every ygpu_postfilter of the context also makes the JUNCTIONS of its batch on
+ * the device.  The contract (yaha_amd/csrc/junction_core.h -- one set of routines for host and device): the eligible records of a read are the printed ones (a
+ * clump that spans two sequences is not) that are primary (status & 0x20) with mapQuality >= min_mapq; their read-forward query interval is (qs, qe) =
+ * status & 1 ? (qlen - 1 - eqo, qlen - 1 - sqo) : (sqo, eqo); ordered by (qs, qe, print order), every consecutive pair (a, b) is one junction with side A =
+ * (sequence of a, its last reference base -- its first when a is reversed --, '+' or '-' when reversed), side B = (sequence of b, its first reference base -- its
+ * last when reversed --, strand) and qgap = qs_b - qe_a - 1 (negative: overlap on the read, positive: unaligned bases between the pieces).  Positions are 0-based
+ * within their sequence.  Canonical form: when (seqB, posB) < (seqA, posA) the sides are swapped and both strands flipped (equal positions: no swap).  Type: TRA
+ * when the sequences differ, else INV when the strands differ, else DEL for +/+ and DUP for -/-.
+ * The junctions of a batch are ordered by (read, ordinal) -- always the same for the same batch -- live in a buffer of the context sized from the batch's filtered
+ * clump count, and are handed out by ygpu_junctions_size / ygpu_junctions_collect, valid after ygpu_postfilter until the context's next ygpu_postfilter (any
+ * number of times, before or after ygpu_collect_filtered).  Reads that come back UNFILTERED (primaryCount == 0xFFFF) get none: the caller filters them and makes
+ * the junctions of what it prints.  Order: ygpu_set_postfilter, ygpu_junctions_enable, then batches.  The table of sequences is copied; a second call replaces
+ * the parameters. */
+enum { YGPU_JUNCTION_DEL = 0, YGPU_JUNCTION_DUP = 1, YGPU_JUNCTION_INV = 2, YGPU_JUNCTION_TRA = 3 };
+typedef struct ygpu_junction {                         /* 32 bytes */
+    uint32_t read;                                     /* index of the read in the batch                          */
+    uint32_t ordinal;                                  /* 0 .. junctions of the read - 1, along the read          */
+    uint32_t seqA, posA, seqB, posB;                   /* canonical: (seqA, posA) <= (seqB, posB)                 */
+    uint8_t  strandA, strandB;                         /* '+' or '-'                                              */
+    uint8_t  type, reserved;                           /* YGPU_JUNCTION_*; 0                                      */
+    int32_t  qgap;
+} ygpu_junction;
+typedef struct ygpu_junction_params {
+    uint32_t min_mapq, n_seqs;
+    const uint32_t *seq_start, *seq_length;            /* reference sequences in bases, ascending (host memory; copied) */
+} ygpu_junction_params;
+int  ygpu_junctions_enable(ygpu_ctx *ctx, const ygpu_junction_params *p);      /* after ygpu_set_postfilter, else YGPU_EINVAL */
+int  ygpu_junctions_size(ygpu_ctx *ctx, uint64_t *n);
+/* out[n] (may be NULL).  stats (may be NULL): reads with junctions, junctions, records skipped by MAPQ, reads left to the caller (handed back unfiltered) --
+ * of this batch. */
+int  ygpu_junctions_collect(ygpu_ctx *ctx, ygpu_junction *out, uint64_t stats[4]);
+
 /* Stage-level entry for tests of the post-filter (as ygpu_dp_batch is for the DP kernels): place a result batch on the device as if ygpu_run had produced it
  * for the reads uploaded last (r->n_reads must equal the uploaded batch's; clump_start / clumps / ops as ygpu_collect returns them).  ygpu_postfilter,
  * ygpu_collect and their siblings then work on it -- so that the device filter can be driven with clump lists no real read produces (hundreds of exact ties,
@@ -362,6 +395,8 @@ int  yaha_session_emit_filtered(yaha_session *s, const ygpu_filtered_batch *r, c
 int  yaha_session_depth_params(yaha_session *s, ygpu_depth_params *p);
 /* The same for ygpu_events_enable: -evbin (default 100), -evq (default 0), -evclip (default 1) and the sequence table (pointers of their own into the session). */
 int  yaha_session_events_params(yaha_session *s, ygpu_events_params *p);
+/* The same for ygpu_junctions_enable: -bpq (default 0) and the sequence table (pointers of their own into the session). */
+int  yaha_session_junction_params(yaha_session *s, ygpu_junction_params *p);
 /* `yaha -g genome.fa [-L k] [-S s] [-H h]`: writes genome.nib2 and genome.X<LL>_<SS>_<HHHHH>S (Main.c:554-628). */
 int  yaha_build_index(int argc, const char *const *argv);
 /* The complete command-line program (index creation or query alignment on the GPU). */

@@ -35,6 +35,9 @@ int  ygpu_depth_collect(ygpu_ctx *, uint32_t *, uint64_t *) { return YGPU_ENODEV
 int  ygpu_events_enable(ygpu_ctx *, const ygpu_events_params *) { return YGPU_ENODEV; }
 int  ygpu_events_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
 int  ygpu_events_collect(ygpu_ctx *, uint32_t *, uint64_t *) { return YGPU_ENODEV; }
+int  ygpu_junctions_enable(ygpu_ctx *, const ygpu_junction_params *) { return YGPU_ENODEV; }
+int  ygpu_junctions_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
+int  ygpu_junctions_collect(ygpu_ctx *, ygpu_junction *, uint64_t *) { return YGPU_ENODEV; }
 void *ygpu_host_alloc(size_t) { return nullptr; }
 void ygpu_host_free(void *) {}
 int  ygpu_submit(ygpu_ctx *, const ygpu_read_batch *, ygpu_ticket *) { return YGPU_ENODEV; }

@@ -86,6 +86,19 @@ class EventsParams(C.Structure):
 EVENTS_CHANNELS = ("mismatch", "deleted", "insertion", "clip_left", "clip_right")
 
 
+class JunctionParams(C.Structure):
+    _fields_ = [("min_mapq", C.c_uint32), ("n_seqs", C.c_uint32), ("seq_start", C.c_void_p), ("seq_length", C.c_void_p)]
+
+
+class Junction(C.Structure):
+    _fields_ = [("read", C.c_uint32), ("ordinal", C.c_uint32), ("seqA", C.c_uint32), ("posA", C.c_uint32), ("seqB", C.c_uint32), ("posB", C.c_uint32),
+                ("strandA", C.c_uint8), ("strandB", C.c_uint8), ("type", C.c_uint8), ("reserved", C.c_uint8), ("qgap", C.c_int32)]
+
+
+JUNCTION_TYPES = ("DEL", "DUP", "INV", "TRA")
+JUNCTION_STATS = ("reads_with_junctions", "junctions", "records_skipped_mapq", "reads_left_to_host")
+
+
 class OutClump(C.Structure):
     _fields_ = [("c", Clump), ("status", C.c_uint8), ("mapQuality", C.c_uint8), ("numSecondaries", C.c_uint16), ("matchedPrimary", C.c_uint16), ("primaryCount", C.c_uint16)]
 
@@ -106,6 +119,7 @@ EXPORTS = (
     "ygpu_device_count", "ygpu_init", "ygpu_init_multi", "ygpu_clone", "ygpu_destroy", "ygpu_last_error", "ygpu_memory", "ygpu_park", "ygpu_get_arena_profile", "ygpu_presize", "ygpu_upload", "ygpu_upload_nowait", "ygpu_run", "ygpu_collect", "ygpu_result_size", "ygpu_collect_into", "ygpu_host_alloc", "ygpu_host_free", "ygpu_set_postfilter", "ygpu_postfilter_snapshot", "ygpu_postfilter", "ygpu_postfilter_drop", "ygpu_inject_results", "ygpu_selftest_primitives", "ygpu_trace_volume", "ygpu_filtered_size", "ygpu_collect_filtered", "ygpu_last_timing",
     "ygpu_depth_enable", "ygpu_depth_size", "ygpu_depth_collect", "yaha_session_depth_params",
     "ygpu_events_enable", "ygpu_events_size", "ygpu_events_collect", "yaha_session_events_params",
+    "ygpu_junctions_enable", "ygpu_junctions_size", "ygpu_junctions_collect", "yaha_session_junction_params",
     "ygpu_submit", "ygpu_poll", "ygpu_wait", "ygpu_seed_join", "ygpu_chain", "ygpu_dp_batch", "ygpu_dp_batch_ex",
     "yaha_session_open", "yaha_session_close", "yaha_session_error", "yaha_session_params",
     "yaha_session_index_view", "yaha_session_header", "yaha_session_next_batch", "yaha_session_emit", "yaha_session_postfilter_params", "yaha_session_emit_filtered",
@@ -310,6 +324,21 @@ class Context:
         ev = np.zeros((max(1, n.value), len(EVENTS_CHANNELS)), dtype=np.uint32); st = (C.c_uint64 * 4)()
         self._check(lib().ygpu_events_collect(self._h, ev.ctypes.data_as(C.POINTER(C.c_uint32)), st), "ygpu_events_collect")
         return ev[:n.value], {k: int(st[i]) for i, k in enumerate(DEPTH_STATS)}
+
+    def junctions_enable(self, session):
+        """Split-read junctions of every batch behind postfilter() (ygpu_junctions_enable), with the session's -bpq and sequence table.  After set_postfilter()."""
+        p = JunctionParams()
+        if lib().yaha_session_junction_params(session._h, C.byref(p)) != 0:
+            raise RuntimeError("yaha_session_junction_params: " + lib().yaha_session_error(session._h).decode())
+        self._check(lib().ygpu_junctions_enable(self._h, C.byref(p)), "ygpu_junctions_enable")
+
+    def junctions_collect(self):
+        """(the junctions of the batch the last postfilter() filtered, in (read, ordinal) order -- a list of Junction -- and the batch's statistics as a dict)."""
+        n = C.c_uint64()
+        self._check(lib().ygpu_junctions_size(self._h, C.byref(n)), "ygpu_junctions_size")
+        out = (Junction * max(1, n.value))(); st = (C.c_uint64 * 4)()
+        self._check(lib().ygpu_junctions_collect(self._h, out, st), "ygpu_junctions_collect")
+        return [out[i] for i in range(n.value)], {k: int(st[i]) for i, k in enumerate(JUNCTION_STATS)}
 
     def inject_results(self, result):
         """Stage-level test entry: a ResultBatch placed on the device as if ygpu_run had produced it for the uploaded reads."""

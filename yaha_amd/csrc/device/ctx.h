@@ -214,6 +214,11 @@ struct ygpu_ctx {
     DevBuf oqCs, oqCl, oqOpsIn, oqSeeds, oqQlen;
     std::shared_ptr<DepthImage> depth;           // set by ygpu_depth_enable: the post-filter then feeds the image's coverage array
     std::shared_ptr<EventsImage> events;         // set by ygpu_events_enable: the post-filter then feeds the image's evidence array
+    // split-read junctions (-obp; junction_stage.h, ../junction_core.h): made per batch behind the post-filter, in buffers of the context's own -- counts and
+    // their exclusive sums per read, the junctions (sized from the batch's filtered clump count), four statistics words, a sequence table of their own
+    DevBuf jnCnt, jnStart, jnOut, jnStats, jnSeqStart, jnSeqLen;
+    bool jnSet = false, jnDone = false, jnHaveTotal = false;       // enabled; the last ygpu_postfilter made them; their number has been fetched
+    uint32_t jnMinMapq = 0, jnNSeqs = 0, jnReads = 0, jnTotal = 0; // jnReads: reads of the batch they belong to (0: an empty batch, nothing on the device)
     // stage state
     uint32_t hOutCounts[2] = {0, 0}, hOutEf = 0;
     bool hOutValid = false;

@@ -1,11 +1,12 @@
 // stage_out.hip -- what leaves the device: the batch's results as ygpu_run left them (ygpu_collect*), and the post-filter stage (postFilterBySimilarity,
 // GraphPath.cpp:897-1086, Query.c:450) on a snapshot of them -- oqc_stage.h -- with its own stream, wait slot and look-back words (PfSide); behind it, when
 // ygpu_depth_enable asked for it, the read-depth track of the printed clumps (depth_stage.h), and when ygpu_events_enable did, their evidence track
-// (events_stage.h).
+// (events_stage.h); and when ygpu_junctions_enable did, the batch's split-read junctions (junction_stage.h), which leave with the filtered batch.
 #include "ctx.h"
 #include "oqc_stage.h"
 #include "depth_stage.h"
 #include "events_stage.h"
+#include "junction_stage.h"
 #include <map>
 
 extern "C" {
@@ -125,13 +126,15 @@ static int postfilterBody(ygpu_ctx *full)
     HIPCHK(hipSetDevice(full->device));
     HIPCHK(hipStreamWaitEvent(ctx->stream, full->evSnap, 0));
     const uint32_t n = full->snapN, C = full->snapC; full->pfN = n; full->nFOut = full->nFOps = 0; full->oqDone = false;
+    full->jnDone = full->jnHaveTotal = false; full->jnReads = 0; full->jnTotal = 0;
     auto takeCounters = [&]() {                                              // (after a wait of this side's stream: the snapshot's copies are done)
         DevCounters dc = full->snapCtr ? *full->snapCtr : full->snapCtrPlain;
         const unsigned long long dropped = dc.v[C_FRAGS]; dc.v[C_HITS] = full->snapHits; dc.v[C_FRAGS] = full->snapFrags + dropped; dc.v[C_REGIONS] = full->snapRegions + dropped;
         memcpy(&full->pfCounters, dc.v, sizeof(ygpu_counters));
     };
     ENSURE(full->oqOutStart, 4ull * (n + 2)); ENSURE(full->oqOpsStart, 4ull * (n + 2));
-    if (n == 0 || C == 0) { HIPCHK(hipMemsetAsync(full->oqOutStart.p, 0, 4ull * (n + 2), ctx->stream)); HIPCHK(streamSync(ctx)); takeCounters(); full->oqDone = true; return 0; }
+    if (n == 0 || C == 0) { HIPCHK(hipMemsetAsync(full->oqOutStart.p, 0, 4ull * (n + 2), ctx->stream)); HIPCHK(streamSync(ctx)); takeCounters(); full->oqDone = true;
+        full->jnDone = full->jnSet; return 0; }
     ENSURE(full->oqNeed, 8ull * (n + 2)); ENSURE(full->oqPoolOff, 8ull * (n + 2)); ENSURE(full->oqLists, 4ull * YQ_NCLASS * (uint64_t)n + 64); ENSURE(full->oqClsCnt, 64);
     ENSURE(full->oqPrim, sizeof(yoqc::CNode) * (uint64_t)C); ENSURE(full->oqPA, sizeof(yoqc::PAttr) * (uint64_t)C); ENSURE(full->oqPush, sizeof(yoqc::OutRec) * (uint64_t)C);
         ENSURE(full->oqOut, sizeof(yoqc::OutRec) * (uint64_t)C);
@@ -192,6 +195,21 @@ static int postfilterBody(ygpu_ctx *full)
     ENSURE(full->oqFClumps, sizeof(ygpu_out_clump) * ((uint64_t)tot[0] + 1)); ENSURE(full->oqFOps, 4ull * ((uint64_t)tot[1] + 1));
     KL(k_oqc_gather, dim3(gridFor((uint64_t)n * 64, 256)), dim3(256), 0, ctx->stream, A, full->oqOutStart.as<uint32_t>(), full->oqOpsStart.as<uint32_t>(),
         full->oqFClumps.as<ygpu_out_clump>(), full->oqFOps.as<uint32_t>());
+    // split-read junctions (-obp): the gathered clumps are in print order, so a wave a read counts its eligible records, the exclusive sum places the reads'
+    // junctions, and a second pass ranks the records and writes them -- ordered by (read, ordinal); nothing is waited for here: ygpu_junctions_size fetches the total
+    if (full->jnSet) {
+        ENSURE(full->jnCnt, 4ull * (n + 2)); ENSURE(full->jnStart, 4ull * (n + 2)); ENSURE(full->jnOut, sizeof(ygpu_junction) * ((uint64_t)tot[0] + 1)); ENSURE(full->jnStats, 64);
+        HIPCHK(hipMemsetAsync(full->jnCnt.p, 0, 4ull * (n + 2), ctx->stream)); HIPCHK(hipMemsetAsync(full->jnStats.p, 0, 64, ctx->stream));
+        JunctionArgs J; J.L = yjunc::layout(full->jnSeqStart.as<uint32_t>(), full->jnSeqLen.as<uint32_t>(), full->jnNSeqs, full->jnMinMapq);
+        J.fClumps = full->oqFClumps.as<ygpu_out_clump>(); J.outStart = full->oqOutStart.as<uint32_t>(); J.qlens = full->oqQlen.as<uint32_t>(); J.nReads = n;
+        J.cnt = full->jnCnt.as<uint32_t>(); J.start = full->jnStart.as<uint32_t>(); J.out = full->jnOut.as<ygpu_junction>(); J.cap = tot[0] + 1;
+        J.stats = full->jnStats.as<unsigned long long>();
+        const dim3 grid(gridFor((uint64_t)n * 64, 256));
+        KL(k_junction_count, grid, dim3(256), 0, ctx->stream, J);
+        rc = cubScan(ctx, full->jnCnt.as<uint32_t>(), full->jnStart.as<uint32_t>(), n + 1); if (rc) return rc;
+        KL(k_junction_emit, grid, dim3(256), 0, ctx->stream, J);
+        full->jnReads = n; full->jnDone = true;
+    }
     // the evidence track (-oev): mismatches, deleted bases, insertions and clipped ends of the clumps just gathered, a wave each, on this stage's stream; the
     // wave finds its clump's read -- the query length of the right clip -- in oqOutStart.  (YGPU_EVENTS_DIRECT: every op's atomics without the combining in the
     // wave, for measurements; read at every call.)
@@ -350,6 +368,69 @@ int ygpu_events_collect(ygpu_ctx *ctx, uint32_t *counts, uint64_t stats[4])
     if (stats) { unsigned long long h[4]; HIPCHK(hipMemcpy(h, EI.stats.p, sizeof h, hipMemcpyDeviceToHost)); for (int k = 0; k < 4; k++) stats[k] = h[k]; }
     return 0;
 }
+// ---- split-read junctions (junction_stage.h; the contract is in ../junction_core.h) --------------------------------------------------------------------------
+// Per batch and per context, unlike the two tracks above: the junctions of the batch the context's last ygpu_postfilter filtered.
+int ygpu_junctions_enable(ygpu_ctx *ctx, const ygpu_junction_params *p)
+{
+    if (!ctx || !ctx->stream || !p) return YGPU_EINVAL;
+    if (!ctx->oqSet) { ctx->err = "ygpu_junctions_enable: ygpu_set_postfilter has not been called on this context (the junctions are made behind the post-filter)";
+        return YGPU_EINVAL; }
+    if (!p->n_seqs || !p->seq_start || !p->seq_length || p->min_mapq > 255) { ctx->err = "ygpu_junctions_enable: bad mapping quality or sequence table"; return YGPU_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    ENSURE(ctx->jnSeqStart, 4ull * p->n_seqs); ENSURE(ctx->jnSeqLen, 4ull * p->n_seqs); ENSURE(ctx->jnStats, 64);
+    HIPCHK(hipMemcpyAsync(ctx->jnSeqStart.p, p->seq_start, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->jnSeqLen.p, p->seq_length, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(streamSync(ctx));
+    ctx->jnMinMapq = p->min_mapq; ctx->jnNSeqs = p->n_seqs; ctx->jnSet = true; ctx->jnDone = false;
+    return 0;
+}
+// the number of junctions of the filtered batch: the last word of the exclusive sums, fetched once (with the flag of a look-back that gave up)
+static int junctionsTotal(ygpu_ctx *full, const char *who)
+{
+    if (!full->jnSet) { full->err = std::string(who) + ": ygpu_junctions_enable has not been called on this context"; return YGPU_EINVAL; }
+    if (!full->jnDone) { full->err = std::string(who) + ": no ygpu_postfilter has run on this context since ygpu_junctions_enable"; return YGPU_EINVAL; }
+    if (full->jnHaveTotal) return 0;
+    if (full->jnReads == 0) { full->jnTotal = 0; full->jnHaveTotal = true; return 0; }
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    uint32_t tot = 0, scanFail = 0;
+    { const FetchPiece pc[2] = {{full->jnStart.as<uint32_t>() + full->jnReads, &tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1}};
+      const int rc = fetchMany(ctx, pc, 2); if (rc) return rc; }
+    if (scanFail) {                                                          // (made clean again for the next batch, as ygpu_postfilter does)
+        HIPCHK(hipMemsetAsync(ctx->counters.as<uint32_t>() + CNT_SCANFAIL, 0, 4, ctx->stream));
+        if (ctx->scanState.p) HIPCHK(hipMemsetAsync(ctx->scanState.p, 0, ctx->scanState.cap, ctx->stream));
+        HIPCHK(streamSync(ctx));
+        ctx->err = "junctions: a look-back of an exclusive sum gave up"; return YGPU_EINTERNAL;
+    }
+    tlsPfFailed = nullptr;
+    if ((uint64_t)tot * sizeof(ygpu_junction) > full->jnOut.cap) { full->err = std::string(who) + ": more junctions than the batch has clumps"; return YGPU_EINTERNAL; }
+    full->jnTotal = tot; full->jnHaveTotal = true;
+    return 0;
+}
+int ygpu_junctions_size(ygpu_ctx *ctx, uint64_t *n)
+{
+    if (!ctx || !ctx->stream || !n) return YGPU_EINVAL;
+    const int rc = junctionsTotal(ctx, "ygpu_junctions_size"); if (rc) return rc;
+    *n = ctx->jnTotal; return 0;
+}
+int ygpu_junctions_collect(ygpu_ctx *full, ygpu_junction *out, uint64_t stats[4])
+{
+    if (!full || !full->stream) return YGPU_EINVAL;
+    const int rc = junctionsTotal(full, "ygpu_junctions_collect"); if (rc) return rc;
+    if (stats) for (int k = 0; k < 4; k++) stats[k] = 0;
+    if (full->jnReads == 0) return 0;
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    unsigned long long h[4] = {0, 0, 0, 0};
+    if (out && full->jnTotal) HIPCHK(hipMemcpyAsync(out, full->jnOut.p, sizeof(ygpu_junction) * (uint64_t)full->jnTotal, hipMemcpyDeviceToHost, ctx->stream));
+    if (stats) HIPCHK(hipMemcpyAsync(h, full->jnStats.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(streamSync(ctx));
+    tlsPfFailed = nullptr;
+    if (stats) for (int k = 0; k < 4; k++) stats[k] = h[k];
+    return 0;
+}
 int ygpu_inject_results(ygpu_ctx *ctx, const ygpu_result_batch *r)
 {
     if (!ctx || !ctx->stream || !r || r->n_reads != ctx->nReads || !r->clump_start || (r->n_clumps && !r->clumps) || (r->n_ops && !r->ops) || r->n_clumps > 0x7FFFFFF0ull
@@ -368,7 +449,7 @@ int ygpu_inject_results(ygpu_ctx *ctx, const ygpu_result_batch *r)
 int ygpu_postfilter_drop(ygpu_ctx *ctx)
 {
     if (!ctx || !ctx->stream) return YGPU_EINVAL;
-    ctx->pfSnap.store(false); ctx->oqDone = false; ctx->nFOut = ctx->nFOps = 0;
+    ctx->pfSnap.store(false); ctx->oqDone = false; ctx->nFOut = ctx->nFOps = 0; ctx->jnDone = false;
     return 0;
 }
 int ygpu_filtered_size(ygpu_ctx *ctx, uint64_t *n_clumps, uint64_t *n_ops)

@@ -3,7 +3,7 @@
 // `yaha -g genome.fa` / `yaha -x index -q reads ...` keep working unchanged.  Extra options of this
 // implementation: -gpus N (shard batches over N devices), -ctx M (contexts per device), -device D, -batch N (reads per device batch),
 // -ocov FILE / -covbin B / -covq Q (read depth of the printed records as bedGraph), -oev FILE / -evbin B / -evq Q / -evclip N (their mismatches, indels and
-// clipped ends per bin).
+// clipped ends per bin), -obp FILE / -bpq Q / -bpw W (split-read breakpoint calls as BEDPE).
 #include "yaha_host.h"
 #include <cstring>
 #include <cstdlib>
@@ -33,7 +33,13 @@ static void usage(FILE *o)
           "       where the printed records disagree with the reference or stop, per bin (the bins of -ocov): mismatched bases, deleted bases, insertions,\n"
           "       records clipped by at least -evclip bases at their left / right end; tab-separated with a header line, bins without events left out, written\n"
           "       after the last alignment.  Accumulated on the device like the depth: 20 bytes a bin of device memory per GPU -- -evbin 1 on a 3.1 Gbp genome\n"
-          "       is 62 GB; when that does not fit the run stops before the first batch and says so (use a larger bin).\n", o);
+          "       is 62 GB; when that does not fit the run stops before the first batch and says so (use a larger bin).\n"
+          "  breakpoints : [-obp bedpeFile|stdout] [-bpq minMapQ (0)] [-bpw clusterWindow (10)]\n"
+          "       where the printed primary alignments of a read join: its records with mapping quality of at least -bpq, ordered along the read, give one\n"
+          "       junction per neighbouring pair (made on the device behind its post-filter); junctions of the same sequences and strands within -bpw bases\n"
+          "       of a cluster's first member on both sides are one cluster.  One BEDPE line per cluster, written after the last alignment: chromA, startA,\n"
+          "       endA, chromB, startB, endB, type (DEL, DUP, INV, TRA), supporting junctions, strandA, strandB, least and largest gap on the read (negative:\n"
+          "       the pieces overlap).\n", o);
 }
 
 static bool parseBool(const char *s, const char *key, bool &out)
@@ -120,6 +126,12 @@ int parseArgs(int argc, char **argv, Args &a)
         else if (is("-evq")) { if (!parseInt(val(), "-evq", a.evMinQ)) return 3; a.haveEvQ = true; }
         else if (is("-evclip")) { if (!parseInt(val(), "-evclip", a.evMinClip)) return 3; a.haveEvClip = true;
             if (a.evMinClip < 1) { fprintf(stderr, "-evclip must be at least 1 (clipped bases).\n\n"); usage(stderr); return 3; } }
+        else if (is("-obp")) { const char *v = val(); a.bpFileName = (!strcmp(v, "-stdout")) ? "stdout" : v; a.haveBp = true;
+            if (a.bpFileName.empty()) { fprintf(stderr, "-obp needs a file name.\n\n"); usage(stderr); return 3; } }
+        else if (is("-bpq")) { if (!parseInt(val(), "-bpq", a.bpMinQ)) return 3; a.haveBpQ = true;
+            if (a.bpMinQ < 0 || a.bpMinQ > 255) { fprintf(stderr, "-bpq must be a mapping quality (0 to 255).\n\n"); usage(stderr); return 3; } }
+        else if (is("-bpw")) { if (!parseInt(val(), "-bpw", a.bpWindow)) return 3; a.haveBpW = true;
+            if (a.bpWindow < 0) { fprintf(stderr, "-bpw must not be negative (bases).\n\n"); usage(stderr); return 3; } }
         else { fprintf(stderr, "%s is not a valid option.\n\n", k); usage(stderr); return 2; }
     }
     a.query = query; a.index = index && !query;
@@ -135,6 +147,13 @@ int parseArgs(int argc, char **argv, Args &a)
         fprintf(stderr, "-oev stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
     if (a.haveEv && a.haveCov && a.evFileName == "stdout" && a.covFileName == "stdout") {
         fprintf(stderr, "-oev stdout: the depth track (-ocov) already goes to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
+    // the breakpoint calls: the same rules once more
+    if (!a.haveBp && (a.haveBpQ || a.haveBpW)) { fprintf(stderr, "-bpq and -bpw need -obp.\n\n"); usage(stderr); return 3; }
+    if (a.haveBp && !query) { fprintf(stderr, "-obp is an output of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return 3; }
+    if (a.haveBp && a.bpFileName == "stdout" && (!a.haveO || a.ofileName == "stdout")) {
+        fprintf(stderr, "-obp stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
+    if (a.haveBp && a.bpFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout"))) {
+        fprintf(stderr, "-obp stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
     if ((a.compress || a.uncompress) && !query) {                                                  // Main.c:472-533: -c wants a FASTA genome, -u a .nib2
         if (!a.haveG) { fprintf(stderr, "Genome file specification (-g) is required for index creation.\n\n"); usage(stderr); return 2; }
         size_t dot = a.gfileName.rfind('.'); const std::string ext = dot == std::string::npos ? "" : a.gfileName.substr(dot);
@@ -202,6 +221,7 @@ std::string samHeader(const Args &a, const Genome &g)                   // outpu
     } else h += " -OQC N";
     if (a.haveCov) { snprintf(buf, sizeof buf, " -covbin %d -covq %d", a.covBin, a.covMinQ); h += " -ocov " + a.covFileName + buf; }
     if (a.haveEv) { snprintf(buf, sizeof buf, " -evbin %d -evq %d -evclip %d", a.evBin, a.evMinQ, a.evMinClip); h += " -oev " + a.evFileName + buf; }
+    if (a.haveBp) { snprintf(buf, sizeof buf, " -bpq %d -bpw %d", a.bpMinQ, a.bpWindow); h += " -obp " + a.bpFileName + buf; }
     h += "\n";
     return h;
 }

@@ -23,11 +23,14 @@ using namespace yaha;
 struct yaha_session {
     Args args; Genome genome; IndexFile index; ReadReader reader; std::string err, header; Text text;
     std::vector<uint32_t> evSeqStart, evSeqLen;                      // what yaha_session_events_params points into
+    std::vector<uint32_t> jnSeqStart, jnSeqLen;                      // what yaha_session_junction_params points into
     std::vector<uint32_t> pfThr, pfSeqStart, pfSeqLen;               // what yaha_session_postfilter_params points into
     std::vector<Read> reads; std::vector<uint8_t> codes; std::vector<uint64_t> offsets;
     bool readerOpen = false;
     DepthTrack *depth = nullptr;                                     // -ocov (the command line): the formatters add the records the device did not count
     EventsTrack *events = nullptr;                                   // -oev: the same for the evidence track
+    // -obp: the formatters make the junctions of the reads the device did not (junctions.cpp) into the batch's own list; their counts of the batch
+    const JunctionTrack *junctions = nullptr; std::vector<ygpu_junction> *jnOut = nullptr; uint64_t jnReads = 0, jnSkipped = 0;
 };
 
 namespace yaha {
@@ -124,20 +127,30 @@ static bool sessionLoad(yaha_session *s)
 
 // OQC/FBS filter + SAM text of one batch.  nt > 1: the reads of the batch are cut into nt contiguous ranges, one thread each (the ctypes/Session path, one
 // batch at a time); the command line formats whole batches on a pool of threads instead (runQueries) and passes nt = 1.
-static void formatRange(const yaha_session *s, const ygpu_result_batch *r, uint32_t i0, uint32_t i1, Text &text, std::vector<OutClump> &oc)
+// the junctions of read i from the records that are printed for it (-obp, host side)
+static void hostJunctions(yaha_session *s, uint32_t i, const OutClump *recs, uint32_t n)
+{
+    uint32_t skipped = 0;
+    if (s->junctions->addRead(recs, n, s->reads[i].len(), i, *s->jnOut, &skipped)) s->jnReads++;
+    s->jnSkipped += skipped;
+}
+static void formatRange(yaha_session *s, const ygpu_result_batch *r, uint32_t i0, uint32_t i1, Text &text, std::vector<OutClump> &oc)
 {
     const Args &a = s->args;
     for (uint32_t i = i0; i < i1; i++) {
         uint32_t c0 = r->clump_start[i], c1 = r->clump_start[i + 1]; int primaryCount = 0;
         postFilter(a, s->genome, s->reads[i], r->clumps + c0, c1 - c0, r->ops, oc, primaryCount);
         for (auto &o : oc) { printClump(a, s->genome, s->reads[i], o, primaryCount, text); if (s->depth) s->depth->add(o); if (s->events) s->events->add(o, s->reads[i].len()); }
+        if (s->junctions && s->jnOut) hostJunctions(s, i, oc.data(), (uint32_t)oc.size());
     }
 }
 // SAM text of a batch whose post-filter ran on the device (ygpu_postfilter): the clumps arrive in print order with the filter's fields set
-// (depthOnDevice / eventsOnDevice: the device stage counted the batch's read depth / evidence track as well -- all but the reads it handed back unfiltered)
-static void formatFiltered(const yaha_session *s, const ygpu_filtered_batch *r, Text &text, bool depthOnDevice = false, bool eventsOnDevice = false)
+// (depthOnDevice / eventsOnDevice / junctionsOnDevice: the device stage counted the batch's read depth / evidence track, made its junctions as well -- all but
+// those of the reads it handed back unfiltered)
+static void formatFiltered(yaha_session *s, const ygpu_filtered_batch *r, Text &text, bool depthOnDevice = false, bool eventsOnDevice = false, bool junctionsOnDevice = false)
 {
     const Args &a = s->args; text.clear();
+    const bool hostJn = s->junctions && s->jnOut;
     std::vector<ygpu_clump> raw; std::vector<OutClump> oc;
     for (uint32_t i = 0; i < r->n_reads; i++) {
         const uint32_t k0 = r->clump_start[i], k1 = r->clump_start[i + 1];
@@ -148,8 +161,10 @@ static void formatFiltered(const yaha_session *s, const ygpu_filtered_batch *r, 
             postFilter(a, s->genome, s->reads[i], raw.data(), k1 - k0, r->ops, oc, primaryCount);
             for (auto &o : oc) { printClump(a, s->genome, s->reads[i], o, primaryCount, text); if (s->depth) s->depth->add(o);
                 if (s->events) s->events->add(o, s->reads[i].len()); }
+            if (hostJn) hostJunctions(s, i, oc.data(), (uint32_t)oc.size());
             continue;
         }
+        if (hostJn && !junctionsOnDevice) oc.clear();
         for (uint32_t k = k0; k < k1; k++) {
             const ygpu_out_clump &f = r->clumps[k];
             OutClump o; o.c = f.c; o.ops = r->ops + f.c.op_start; o.status = f.status; o.mapQuality = f.mapQuality; o.numSecondaries = f.numSecondaries;
@@ -157,7 +172,9 @@ static void formatFiltered(const yaha_session *s, const ygpu_filtered_batch *r, 
             printClump(a, s->genome, s->reads[i], o, (int)f.primaryCount, text);
             if (s->depth && !depthOnDevice) s->depth->add(o);
             if (s->events && !eventsOnDevice) s->events->add(o, s->reads[i].len());
+            if (hostJn && !junctionsOnDevice) oc.push_back(o);
         }
+        if (hostJn && !junctionsOnDevice && k1 - k0 >= 2) hostJunctions(s, i, oc.data(), (uint32_t)oc.size());
     }
 }
 static void formatBatch(yaha_session *s, const ygpu_result_batch *r, Text &text, int nt)
@@ -222,6 +239,9 @@ int runQueries(Args &a, FILE *log)
     // -oev: the same for the evidence track (events.cpp)
     std::unique_ptr<EventsTrack> events;
     if (A.haveEv) { events.reset(new EventsTrack); if (!events->init(S->genome, A.evBin, A.evMinQ, A.evMinClip, S->err)) { fprintf(log, "%s\n", S->err.c_str()); return 1; } }
+    // -obp: the run's junctions (junctions.cpp); a batch's are made on the device behind its post-filter and travel with it
+    std::unique_ptr<JunctionTrack> junctions;
+    if (A.haveBp) { junctions.reset(new JunctionTrack); junctions->init(S->genome, A.bpMinQ, A.bpWindow); }
     setvbuf(out, nullptr, _IONBF, 0);                                       // whole batches are written with one call each
     if (fputs(S->header.c_str(), out) < 0) { fprintf(log, "Failure writing the output file.\n"); return 1; }
     ygpu_params P; paramsFromArgs(A, P);
@@ -258,6 +278,8 @@ int runQueries(Args &a, FILE *log)
     };
     struct Batch { uint64_t ticket = 0; std::vector<Span> spans; std::vector<Read> reads; size_t nReads = 0; std::vector<uint8_t> codes; std::vector<uint64_t> offsets;
                    ResBuf clumpStart, ops, clumps; uint64_t nClumps = 0, nOps = 0; bool filtered = false, depthOnDevice = false, eventsOnDevice = false; Text text;
+                   // -obp: the junctions the device made of the batch and its statistics; the ones the formatter made, and its counts
+                   bool junctionsOnDevice = false; std::vector<ygpu_junction> jnDev, jnHost; uint64_t jnDevStats[4] = {0, 0, 0, 0}, jnHostReads = 0, jnHostSkipped = 0;
                    double tRead = 0, tDev = 0, tFmt = 0; };
     typedef std::unique_ptr<Batch> BatchP;
     struct Pool { std::mutex mu; std::vector<BatchP> free; BatchP get() { { std::lock_guard<std::mutex> lk(mu); if (!free.empty()) { BatchP b = std::move(free.back());
@@ -336,6 +358,8 @@ int runQueries(Args &a, FILE *log)
     // the evidence track on the device: the same arrangement (YAHA_HOST_EVENTS: the formatters count everything)
     const bool eventsDevice = events && deviceFilter && EventsTrack::deviceEntryPoints() && getenv("YAHA_HOST_EVENTS") == nullptr;
     std::vector<std::atomic<int>> eventsCtx(nDev); for (auto &x : eventsCtx) x = 0;
+    // the junctions on the device: per context and per batch, nothing shared (YAHA_HOST_JUNCTIONS: the formatters make them all)
+    const bool junctionsDevice = junctions && deviceFilter && JunctionTrack::deviceEntryPoints() && getenv("YAHA_HOST_JUNCTIONS") == nullptr;
     std::vector<std::atomic<uint64_t>> devReads(nDev); for (auto &x : devReads) x = 0;       // reads each device took (the stats line: do all devices pull their weight?)
     // where a context thread's time goes, batches after a context's first (the stats line; microseconds): upload, run, waiting for the filter thread, snapshot; and the filter
     // thread's post-filter + collect
@@ -377,6 +401,7 @@ int runQueries(Args &a, FILE *log)
             if (rcE == YGPU_ENOMEM) { char m[640]; snprintf(m, sizeof m, "-oev: %s", ygpu_last_error(ctx[d])); fail(m); }
             else if (rcE == 0) { ctxEvents = true; int none = 0; eventsCtx[d / perDev].compare_exchange_strong(none, d + 1); }
         }
+        const bool ctxJunctions = rc0 == 0 && junctionsDevice && junctions->deviceEnable(ctx[d]) == 0;      // (refused: the formatters make this context's)
         if (rc0 != 0) { char m[512];
             snprintf(m, sizeof m, "ygpu_init(device %d) failed: %d %s", dev, rc0, ctx[d] ? ygpu_last_error(ctx[d]) : (d == leadCtx ? "" : "(the device's first context failed)"));
             fail(m); }
@@ -399,6 +424,8 @@ int runQueries(Args &a, FILE *log)
         auto collectFiltered = [&](BatchP &fb, ygpu_result_batch &res) -> int {
             uint64_t nc = 0, no = 0;
             int rc = ygpu_postfilter(ctx[d]); if (rc == 0) rc = ygpu_filtered_size(ctx[d], &nc, &no); if (rc != 0) return rc;
+            // (the batch's junctions: few, and on their way while the clumps are sized)
+            if (fb->junctionsOnDevice) { rc = junctions->deviceCollect(ctx[d], fb->jnDev, fb->jnDevStats); if (rc != 0) return rc; }
             if (!fb->clumpStart.ensure(4 * (fb->nReads + 1)) || !fb->clumps.ensure(sizeof(ygpu_out_clump) * nc) || !fb->ops.ensure(4 * no)) return YGPU_ENOMEM;
             ygpu_filtered_batch fr; rc = ygpu_collect_filtered(ctx[d], (uint32_t *)fb->clumpStart.p, (ygpu_out_clump *)fb->clumps.p, (uint32_t *)fb->ops.p, &fr);
             res.n_clumps = fr.n_clumps; res.n_ops = fr.n_ops; return rc;
@@ -470,6 +497,7 @@ int runQueries(Args &a, FILE *log)
                 int rc = ygpu_upload_nowait(ctx[d], &rb); const double h1 = now(); if (rc == 0) rc = ygpu_run(ctx[d]); if (rc != 0) return rc;
                 const double h2 = now();
                 uint64_t nc = 0, no = 0; b->filtered = deviceFilter; b->depthOnDevice = deviceFilter && ctxDepth; b->eventsOnDevice = deviceFilter && ctxEvents;
+                b->junctionsOnDevice = deviceFilter && ctxJunctions;
                 if (!first) { usUpload += (uint64_t)((h1 - h0) * 1e3); usRun += (uint64_t)((h2 - h1) * 1e3); nLater++; }
                 if (deviceFilter && overlapFilter && !first) {                 // the filter thread takes it from here; this thread goes on with the next batch
                     filterIdle();
@@ -516,21 +544,24 @@ int runQueries(Args &a, FILE *log)
     auto formatter = [&]() {
         yaha_session local; local.args = A; local.genome.bases = S->genome.bases; local.genome.nBaseBytes = S->genome.nBaseBytes; local.genome.seqs = S->genome.seqs;
             local.genome.maxROff = S->genome.maxROff;
-        local.depth = depth.get(); local.events = events.get();
+        local.depth = depth.get(); local.events = events.get(); local.junctions = junctions.get();
         BatchP b;
         while (fmtQ.pop(b)) {
             const double t0 = now(); b->text.clear();
+            b->jnHost.clear(); local.jnOut = &b->jnHost; local.jnReads = local.jnSkipped = 0;
+            if (!(b->nReads && b->filtered && b->junctionsOnDevice)) { b->jnDev.clear(); b->junctionsOnDevice = false; memset(b->jnDevStats, 0, sizeof b->jnDevStats); }
             if (!stop && b->nReads && b->filtered) {
                 ygpu_filtered_batch fr; memset(&fr, 0, sizeof fr);
                 fr.n_reads = (uint32_t)b->nReads; fr.clump_start = (const uint32_t *)b->clumpStart.p; fr.clumps = (const ygpu_out_clump *)b->clumps.p;
                     fr.ops = (const uint32_t *)b->ops.p; fr.n_clumps = b->nClumps; fr.n_ops = b->nOps;
-                local.reads.swap(b->reads); formatFiltered(&local, &fr, b->text, b->depthOnDevice, b->eventsOnDevice); local.reads.swap(b->reads);
+                local.reads.swap(b->reads); formatFiltered(&local, &fr, b->text, b->depthOnDevice, b->eventsOnDevice, b->junctionsOnDevice); local.reads.swap(b->reads);
             } else if (!stop && b->nReads) {
                 ygpu_result_batch res; memset(&res, 0, sizeof res);
                 res.n_reads = (uint32_t)b->nReads; res.clump_start = (const uint32_t *)b->clumpStart.p; res.clumps = (const ygpu_clump *)b->clumps.p;
                     res.ops = (const uint32_t *)b->ops.p; res.n_clumps = b->nClumps; res.n_ops = b->nOps;
                 local.reads.swap(b->reads); formatBatch(&local, &res, b->text, 1); local.reads.swap(b->reads);
             }
+            b->jnHostReads = local.jnReads; b->jnHostSkipped = local.jnSkipped;
             b->tFmt = now() - t0;
             outQ.push(std::move(b));
         }
@@ -546,6 +577,7 @@ int runQueries(Args &a, FILE *log)
                 if (!stop) {
                     if (w->text.len && fwrite(w->text.p, 1, w->text.len, out) != w->text.len) fail("Failure writing the output file");
                     else { const double t = now(); if (nWritten == 0) { tFirstOut = t; nFirst = w->nReads; } tLastOut = t; nWritten += w->nReads; }
+                    if (junctions && w->nReads) junctions->addBatch(w->jnDev.data(), w->jnDev.size(), w->jnDevStats, w->jnHost, w->jnHostReads, w->jnHostSkipped);
                     if (timing) fprintf(stderr, "[yaha] ticket %llu: %zu reads  parse %.1f  device (upload, run, collect) %.1f  format %.1f ms  written at %.1f\n",
                         (unsigned long long)w->ticket, w->nReads, w->tRead, w->tDev, w->tFmt, now() - tEnter);
                 }
@@ -588,6 +620,13 @@ int runQueries(Args &a, FILE *log)
         if (fflush(out) != 0) rcAll = 1;
         if (rcAll == 0 && !events->write(A.evFileName.c_str(), S->genome, eerr)) { fprintf(log, "%s\n", eerr.c_str()); rcAll = 1; }
     }
+    // the breakpoint calls: the run's junctions clustered and written, after the tracks
+    uint64_t nJunctions = 0;
+    if (junctions && !stop && rcAll == 0) {
+        std::string jerr; nJunctions = junctions->all.size();
+        if (fflush(out) != 0) rcAll = 1;
+        if (rcAll == 0 && !junctions->write(A.bpFileName.c_str(), S->genome, jerr)) { fprintf(log, "%s\n", jerr.c_str()); rcAll = 1; }
+    }
     const bool fastExit = getenv("YAHA_FAST_EXIT") != nullptr;
     if (!fastExit) for (int d = ngpu - 1; d >= 0; d--) if (ctx[d]) ygpu_destroy(ctx[d]);     // clones before their parents
     // (the batches -- a million small strings, the page-locked buffers -- go with the process as well: freeing them one by one was 0.3 s)
@@ -600,12 +639,15 @@ int runQueries(Args &a, FILE *log)
         std::string per = "[";
         for (int k = 0; k < nDev; k++) { char t[32]; snprintf(t, sizeof t, "%s%llu", k ? ", " : "", (unsigned long long)devReads[k].load()); per += t; }
         per += "]";
-        char dstat[512] = "";
+        char dstat[768] = "";
         if (depth) snprintf(dstat, sizeof dstat, ", \"depth_bins\": %llu, \"depth_device_records\": %llu, \"depth_host_records\": %llu, \"depth_covered_bases\": %llu",
             (unsigned long long)depth->nBins, (unsigned long long)depth->devRecords, (unsigned long long)depth->hostRecords, (unsigned long long)depth->coveredBases());
         if (events) { const size_t at = strlen(dstat);
             snprintf(dstat + at, sizeof dstat - at, ", \"events_bins\": %llu, \"events_device_records\": %llu, \"events_host_records\": %llu, \"events_counted\": %llu",
                 (unsigned long long)events->nBins, (unsigned long long)events->devRecords, (unsigned long long)events->hostRecords, (unsigned long long)events->counted()); }
+        if (junctions) { const size_t at = strlen(dstat);
+            snprintf(dstat + at, sizeof dstat - at, ", \"bp_device_reads\": %llu, \"bp_host_reads\": %llu, \"bp_junctions\": %llu, \"bp_clusters\": %llu",
+                (unsigned long long)junctions->devReads, (unsigned long long)junctions->hostReads, (unsigned long long)nJunctions, (unsigned long long)junctions->nClusters); }
         fprintf(stderr, "[yaha] stats {\"reads\": %llu, \"contexts_up_ms\": %.1f, \"first_batch_written_ms\": %.1f, \"last_batch_written_ms\": %.1f, \"total_ms\": %.1f, "
             "\"steady_reads_per_s\": %.0f, \"cpus\": %d, \"formatters\": %d, \"parsers\": %d, \"gpus\": %d, \"ctx_per_gpu\": %d, \"ctx_left_out\": %d, "
             "\"reads_per_device\": %s, \"context_thread_ms_per_batch\": {\"wait_for_a_batch\": %.2f, \"upload\": %.2f, \"run\": %.2f, \"wait_for_filter_thread\": %.2f, "
@@ -679,6 +721,13 @@ int yaha_session_events_params(yaha_session *s, ygpu_events_params *p)
     s->evSeqStart.clear(); s->evSeqLen.clear(); for (auto &sq : s->genome.seqs) { s->evSeqStart.push_back(sq.start); s->evSeqLen.push_back(sq.length); }
     p->bin = (uint32_t)s->args.evBin; p->min_mapq = (uint32_t)s->args.evMinQ; p->min_clip = (uint32_t)s->args.evMinClip; p->n_seqs = (uint32_t)s->evSeqStart.size();
         p->seq_start = s->evSeqStart.data(); p->seq_length = s->evSeqLen.data();
+    return 0;
+}
+int yaha_session_junction_params(yaha_session *s, ygpu_junction_params *p)
+{
+    if (!s || !p) return YGPU_EINVAL;
+    s->jnSeqStart.clear(); s->jnSeqLen.clear(); for (auto &sq : s->genome.seqs) { s->jnSeqStart.push_back(sq.start); s->jnSeqLen.push_back(sq.length); }
+    p->min_mapq = (uint32_t)s->args.bpMinQ; p->n_seqs = (uint32_t)s->jnSeqStart.size(); p->seq_start = s->jnSeqStart.data(); p->seq_length = s->jnSeqLen.data();
     return 0;
 }
 int yaha_session_emit_filtered(yaha_session *s, const ygpu_filtered_batch *r, const char **text, size_t *len)

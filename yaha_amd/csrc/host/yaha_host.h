@@ -75,6 +75,8 @@ struct Args {
     bool haveCov = false, haveCovBin = false, haveCovQ = false; std::string covFileName; int covBin = 100, covMinQ = 0;
     // evidence track: -oev FILE (mismatch / deleted / insertion / clipped-end counts per bin), -evbin B, -evq Q, -evclip N (a clip counts from N bases on)
     bool haveEv = false, haveEvBin = false, haveEvQ = false, haveEvClip = false; std::string evFileName; int evBin = 100, evMinQ = 0, evMinClip = 1;
+    // breakpoint calls: -obp FILE (BEDPE, one line a cluster of split-read junctions), -bpq Q (records below this mapping quality join nothing), -bpw W (cluster window)
+    bool haveBp = false, haveBpQ = false, haveBpW = false; std::string bpFileName; int bpMinQ = 0, bpWindow = 10;
     bool query = false, index = true, compress = false, uncompress = false;   // -c / -u: .fa -> .nib2 / .nib2 -> .fasta only (Main.c:284-293, non-user builds of the reference)
 };
 void postProcessArgs(Args &a, bool query);                                  // AlignArgs.c:108-169
@@ -178,6 +180,26 @@ struct EventsTrack {
     int  deviceCollect(ygpu_ctx *ctx, std::string &err);                  // adds the image's array and statistics to this track
     uint64_t counted() const;                                             // the sum over all bins and channels
     bool write(const char *path, const Genome &g, std::string &err) const;      // path "stdout" = standard output
+};
+
+// ---- split-read breakpoint calls (-obp; junctions.cpp, ../junction_core.h) ---------------------------------------------------------------------------------
+// The junctions of the whole run, their clustering and the BEDPE writer.  The junctions of a batch are made on the device behind its post-filter
+// (ygpu_junctions_*, looked up weakly as the tracks' entry points are) and travel with the batch; the formatter threads make the ones the device did not -- the
+// reads it handed back unfiltered, runs whose post-filter stays on the host, builds without the entry points -- with the same routine (junction_core.h).  The
+// writer thread adds every batch's junctions in ticket order, merged by read: the list is in read order whatever -ctx and -batch are.
+struct JunctionTrack {
+    std::vector<uint32_t> seqStart, seqLength; uint32_t minMapq = 0, window = 10;
+    std::vector<ygpu_junction> all;                                       // (read: the index within its batch; not used after the merge)
+    uint64_t devReads = 0, hostReads = 0, devSkipped = 0, hostSkipped = 0, devHandedBack = 0, nClusters = 0;      // reads with junctions by who made them ...
+    void init(const Genome &g, int minQ, int w);
+    // the junctions of one read's printed records on the host, appended to out (ordinal order); returns their number; *skipped: records gated by MAPQ alone
+    uint32_t addRead(const OutClump *recs, uint32_t n, int qlen, uint32_t read, std::vector<ygpu_junction> &out, uint32_t *skipped) const;
+    // one batch, in output order: the device's junctions (read order) and the formatter's (read order) merged by read; hostReadsB / hostSkippedB: the formatter's counts
+    void addBatch(const ygpu_junction *dev, size_t nDev, const uint64_t devStats[4], const std::vector<ygpu_junction> &host, uint64_t hostReadsB, uint64_t hostSkippedB);
+    static bool deviceEntryPoints();                                      // does this build have ygpu_junctions_*?
+    int  deviceEnable(ygpu_ctx *ctx) const;                               // YGPU_ENODEV without the entry points
+    int  deviceCollect(ygpu_ctx *ctx, std::vector<ygpu_junction> &out, uint64_t stats[4]) const;      // the junctions of the context's last ygpu_postfilter
+    bool write(const char *path, const Genome &g, std::string &err);      // clusters and writes; path "stdout" = standard output
 };
 }  // namespace yaha
 namespace yoqc { struct Params; }
