@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import depth_oracle as do
+import events_oracle as eo
 import yaha_amd as ya
 from conftest import golden_lines, strip_pg
 
@@ -96,6 +97,44 @@ def test_abi_batches_accumulate_and_contexts_of_an_image_share_one_array(work, i
             with ya.Session(["-x", index11, "-q", os.path.join(work, "rchim.fa"), "-osh", "stdout", "-ocov", "unused.bg", "-covbin", "50"]) as s2:
                 with pytest.raises(RuntimeError):
                     a.depth_enable(s2)
+
+
+def test_depth_and_evidence_arrays_of_an_image_are_two_arrays_with_their_own_bins(work, index11):
+    """Both kinds on the contexts of one image, with different bin sizes (37 and 50): the arrays live in one registry and one struct, so a key that did not tell
+    the kinds apart, or one array serving both, shows as a wrong length or wrong counts.  Exact against the two oracles after every batch."""
+    q = os.path.join(work, "rchim.fa"); BD, BE, CLIP = 37, 50, 3
+
+    def session(covbin, evbin):
+        return ya.Session(["-x", index11, "-q", q, "-osh", "stdout", "-ocov", "x", "-covbin", str(covbin), "-oev", "y", "-evbin", str(evbin), "-evclip", str(CLIP)])
+
+    with session(BD, BE) as s:
+        sq = do.sq_table(s.header().split("\n"))
+        with ya.Context(s.index, s.params) as a:
+            a.set_postfilter(s); a.depth_enable(s); a.events_enable(s)
+            with ya.Context(s.index, s.params, parent=a) as b:
+                b.set_postfilter(s); b.depth_enable(s); b.events_enable(s)
+                lines = []
+                for k, ctx in enumerate((a, a, b, a, b)):
+                    rb = s.next_batch(40)
+                    assert rb.n_reads > 0
+                    ctx.upload(rb); ctx.run()
+                    lines += s.emit_filtered(ctx.postfilter()).split("\n")
+                    cov, _ = ctx.depth_collect(); ev, _ = ctx.events_collect()
+                    assert np.array_equal(cov, np.array(do.coverage(lines, sq, BD, 0), dtype=np.uint32)), k
+                    assert np.array_equal(ev, np.array(eo.events(lines, sq, BE, 0, CLIP), dtype=np.uint32).reshape(-1, 5)), k
+                (ca, _), (cb, _), (ea, _), (eb, _) = a.depth_collect(), b.depth_collect(), a.events_collect(), b.events_collect()
+                assert len(ca) == do.n_bins(sq, BD) != do.n_bins(sq, BE) == len(ea)
+                assert np.array_equal(ca, cb) and np.array_equal(ea, eb)
+                assert ca.sum() > 0 and all(t > 0 for t in ea.sum(axis=0)), (ca.sum(), ea.sum(axis=0))
+                # a second enable of either kind with the OTHER kind's bin size is refused, and leaves the other kind's array alone
+                with session(BE, BE) as s2:
+                    with pytest.raises(RuntimeError, match="ygpu_depth_enable.*other parameters"):
+                        a.depth_enable(s2)
+                assert np.array_equal(a.events_collect()[0], ea) and np.array_equal(a.depth_collect()[0], ca)
+                with session(BD, BD) as s3:
+                    with pytest.raises(RuntimeError, match="ygpu_events_enable.*other parameters"):
+                        a.events_enable(s3)
+                assert np.array_equal(a.depth_collect()[0], ca) and np.array_equal(a.events_collect()[0], ea)
 
 
 # (the sessions below take -covbin / -covq from their arguments, and those need -ocov; a session never writes the file)

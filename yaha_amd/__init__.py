@@ -291,54 +291,55 @@ class Context:
             raise RuntimeError("yaha_session_postfilter_params: " + lib().yaha_session_error(session._h).decode())
         self._check(lib().ygpu_set_postfilter(self._h, C.byref(p)), "ygpu_set_postfilter")
 
+    def _enable(self, fill, enable, params, session):
+        """enable(context, params) -- a ygpu_*_enable -- with the parameters fill -- the yaha_session_*_params that goes with it -- takes from the session."""
+        if fill(session._h, C.byref(params)) != 0:
+            raise RuntimeError(fill.__name__ + ": " + lib().yaha_session_error(session._h).decode())
+        self._check(enable(self._h, C.byref(params)), enable.__name__)
+
+    def _collect(self, size, collect, make, stat_names):
+        """size(context, n) -- a ygpu_*_size --, then collect -- the ygpu_*_collect that goes with it -- into make(n): (the object to return, what the call
+        fills); returns (object, n, the statistics as a dict)."""
+        n = C.c_uint64()
+        self._check(size(self._h, C.byref(n)), size.__name__)
+        out, arg = make(n.value); st = (C.c_uint64 * 4)()
+        self._check(collect(self._h, arg, st), collect.__name__)
+        return out, n.value, {k: int(st[i]) for i, k in enumerate(stat_names)}
+
+    @staticmethod
+    def _bins(shape):
+        import numpy as np
+        a = np.zeros(shape, dtype=np.uint32)
+        return a, a.ctypes.data_as(C.POINTER(C.c_uint32))
+
     def depth_enable(self, session):
         """Read depth of the printed clumps behind postfilter() (ygpu_depth_enable), with the session's -covbin / -covq and sequence table.  After
         set_postfilter(); the contexts of one index image share one array."""
-        p = DepthParams()
-        if lib().yaha_session_depth_params(session._h, C.byref(p)) != 0:
-            raise RuntimeError("yaha_session_depth_params: " + lib().yaha_session_error(session._h).decode())
-        self._check(lib().ygpu_depth_enable(self._h, C.byref(p)), "ygpu_depth_enable")
+        self._enable(lib().yaha_session_depth_params, lib().ygpu_depth_enable, DepthParams(), session)
 
     def depth_collect(self):
         """(coverage array of the context's index image as it stands -- one uint32 per bin, a numpy array -- and the statistics as a dict)."""
-        import numpy as np
-        n = C.c_uint64()
-        self._check(lib().ygpu_depth_size(self._h, C.byref(n)), "ygpu_depth_size")
-        bins = np.zeros(max(1, n.value), dtype=np.uint32); st = (C.c_uint64 * 4)()
-        self._check(lib().ygpu_depth_collect(self._h, bins.ctypes.data_as(C.POINTER(C.c_uint32)), st), "ygpu_depth_collect")
-        return bins[:n.value], {k: int(st[i]) for i, k in enumerate(DEPTH_STATS)}
+        bins, n, st = self._collect(lib().ygpu_depth_size, lib().ygpu_depth_collect, lambda n: self._bins(max(1, n)), DEPTH_STATS)
+        return bins[:n], st
 
     def events_enable(self, session):
         """The evidence track of the printed clumps behind postfilter() (ygpu_events_enable), with the session's -evbin / -evq / -evclip and sequence table.
         After set_postfilter(); the contexts of one index image share one array."""
-        p = EventsParams()
-        if lib().yaha_session_events_params(session._h, C.byref(p)) != 0:
-            raise RuntimeError("yaha_session_events_params: " + lib().yaha_session_error(session._h).decode())
-        self._check(lib().ygpu_events_enable(self._h, C.byref(p)), "ygpu_events_enable")
+        self._enable(lib().yaha_session_events_params, lib().ygpu_events_enable, EventsParams(), session)
 
     def events_collect(self):
         """(evidence array of the context's index image as it stands -- numpy uint32 of shape (n_bins, 5), channels EVENTS_CHANNELS -- and the statistics as a dict)."""
-        import numpy as np
-        n = C.c_uint64()
-        self._check(lib().ygpu_events_size(self._h, C.byref(n)), "ygpu_events_size")
-        ev = np.zeros((max(1, n.value), len(EVENTS_CHANNELS)), dtype=np.uint32); st = (C.c_uint64 * 4)()
-        self._check(lib().ygpu_events_collect(self._h, ev.ctypes.data_as(C.POINTER(C.c_uint32)), st), "ygpu_events_collect")
-        return ev[:n.value], {k: int(st[i]) for i, k in enumerate(DEPTH_STATS)}
+        ev, n, st = self._collect(lib().ygpu_events_size, lib().ygpu_events_collect, lambda n: self._bins((max(1, n), len(EVENTS_CHANNELS))), DEPTH_STATS)
+        return ev[:n], st
 
     def junctions_enable(self, session):
         """Split-read junctions of every batch behind postfilter() (ygpu_junctions_enable), with the session's -bpq and sequence table.  After set_postfilter()."""
-        p = JunctionParams()
-        if lib().yaha_session_junction_params(session._h, C.byref(p)) != 0:
-            raise RuntimeError("yaha_session_junction_params: " + lib().yaha_session_error(session._h).decode())
-        self._check(lib().ygpu_junctions_enable(self._h, C.byref(p)), "ygpu_junctions_enable")
+        self._enable(lib().yaha_session_junction_params, lib().ygpu_junctions_enable, JunctionParams(), session)
 
     def junctions_collect(self):
         """(the junctions of the batch the last postfilter() filtered, in (read, ordinal) order -- a list of Junction -- and the batch's statistics as a dict)."""
-        n = C.c_uint64()
-        self._check(lib().ygpu_junctions_size(self._h, C.byref(n)), "ygpu_junctions_size")
-        out = (Junction * max(1, n.value))(); st = (C.c_uint64 * 4)()
-        self._check(lib().ygpu_junctions_collect(self._h, out, st), "ygpu_junctions_collect")
-        return [out[i] for i in range(n.value)], {k: int(st[i]) for i, k in enumerate(JUNCTION_STATS)}
+        out, n, st = self._collect(lib().ygpu_junctions_size, lib().ygpu_junctions_collect, lambda n: ((Junction * max(1, n))(),) * 2, JUNCTION_STATS)
+        return [out[i] for i in range(n)], st
 
     def inject_results(self, result):
         """Stage-level test entry: a ResultBatch placed on the device as if ygpu_run had produced it for the uploaded reads."""

@@ -115,28 +115,19 @@ struct PfSide {
     int device = 0;
 };
 
-// Read depth along the reference (-ocov; depth_stage.h, ../depth_core.h): ONE coverage array per index image -- 4 bytes a bin -- which the contexts that share
-// the image (ygpu_clone, ctx_per_device of ygpu_init_multi) feed together with global atomics.  Made by the first ygpu_depth_enable of the image, held by every
+// The binned tracks behind the post-filter -- read depth (-ocov; depth_stage.h, ../depth_core.h: one uint32 a bin) and the evidence track (-oev; events_stage.h,
+// ../events_core.h: yevents::NCH uint32 channels a bin) -- keep ONE array per kind and index image, which the contexts that share the image (ygpu_clone,
+// ctx_per_device of ygpu_init_multi) feed together with global atomics.  Made by the image's first ygpu_depth_enable / ygpu_events_enable, held by every
 // context that enabled it, released with the last of them (never by ygpu_park: a parked sibling keeps its reference and gives up nothing of the image's).
-struct DepthImage {
+// The two arrays of an image are independent: each has its own bins, gates and sequence table.
+enum { TRACK_DEPTH = 0, TRACK_EVENTS = 1, TRACK_KINDS };
+struct TrackImage {
     int device = 0;
-    DevBuf cov, stats, seqStart, seqLength, binBase;
+    DevBuf data, stats, seqStart, seqLength, binBase;
     uint64_t nBins = 0;
-    uint32_t bin = 0, minMapq = 0;
+    uint32_t channels = 1, bin = 0, minMapq = 0, minClip = 0;     // (minClip: 0 for depth)
     std::vector<uint32_t> hSeqStart, hSeqLength;                  // what it was enabled with (a second enable must agree)
-    ~DepthImage() { (void)hipSetDevice(device); cov.release(); stats.release(); seqStart.release(); seqLength.release(); binBase.release(); }
-};
-
-// The evidence track (-oev; events_stage.h, ../events_core.h): ONE array per index image as well -- five uint32 channels a bin, 20 bytes a bin, on -ocov's bin
-// layout -- with the life cycle of DepthImage: made by the image's first ygpu_events_enable, held by every context that enabled it, untouched by ygpu_park.
-// It keeps a sequence table of its own, so that it does not depend on depth being enabled.
-struct EventsImage {
-    int device = 0;
-    DevBuf ev, stats, seqStart, seqLength, binBase;
-    uint64_t nBins = 0;
-    uint32_t bin = 0, minMapq = 0, minClip = 0;
-    std::vector<uint32_t> hSeqStart, hSeqLength;                  // what it was enabled with (a second enable must agree)
-    ~EventsImage() { (void)hipSetDevice(device); ev.release(); stats.release(); seqStart.release(); seqLength.release(); binBase.release(); }
+    ~TrackImage() { (void)hipSetDevice(device); data.release(); stats.release(); seqStart.release(); seqLength.release(); binBase.release(); }
 };
 
 struct ygpu_ctx {
@@ -212,8 +203,7 @@ struct ygpu_ctx {
     DevCounters snapCtrPlain{};
     unsigned long long snapHits = 0, snapFrags = 0, snapRegions = 0;
     DevBuf oqCs, oqCl, oqOpsIn, oqSeeds, oqQlen;
-    std::shared_ptr<DepthImage> depth;           // set by ygpu_depth_enable: the post-filter then feeds the image's coverage array
-    std::shared_ptr<EventsImage> events;         // set by ygpu_events_enable: the post-filter then feeds the image's evidence array
+    std::shared_ptr<TrackImage> track[TRACK_KINDS];      // set by ygpu_depth_enable / ygpu_events_enable: the post-filter then feeds the image's array of that kind
     // split-read junctions (-obp; junction_stage.h, ../junction_core.h): made per batch behind the post-filter, in buffers of the context's own -- counts and
     // their exclusive sums per read, the junctions (sized from the batch's filtered clump count), four statistics words, a sequence table of their own
     DevBuf jnCnt, jnStart, jnOut, jnStats, jnSeqStart, jnSeqLen;

@@ -8,8 +8,7 @@
 // the lanes: neighbouring lanes add to neighbouring words, one atomic per (run, bin).  The array is shared by the contexts of an index image; plain global
 // atomicAdd on uint32 (no value returned, device scope) makes that safe.
 #pragma once
-#include "common.h"
-#include "../depth_core.h"
+#include "track_stage.h"
 
 struct DepthArgs {
     ydepth::Layout L;
@@ -23,28 +22,22 @@ __global__ void __launch_bounds__(256) k_depth_clumps(DepthArgs D, const ygpu_ou
     if (w >= nClumps) return;
     const ygpu_out_clump f = fClumps[w];
     if (f.primaryCount == 0xFFFFu) return;                                  // a read handed back unfiltered: the host filters it and counts what it prints
-    int seq = -1; const int g = ydepth::gate(D.L, f.c, f.mapQuality, &seq);
-    if (lane == 0) atomicAdd(D.stats + g, 1ull);
-    if (g != ydepth::COUNTED) return;
+    int seq = -1;
+    if (!trackGate(D.L, f, D.stats, lane, &seq)) return;
     uint32_t *const cov = D.cov; const uint32_t nBins = D.nBins;
     auto add = [cov, nBins](uint32_t b, uint32_t n) { if (b < nBins) atomicAdd(cov + b, n); };
     const uint32_t *ops = fOps + f.c.op_start; const uint32_t nOps = f.c.n_ops;
     uint32_t cur = f.c.sro, runStart = f.c.sro;                             // (the same on every lane)
     for (uint32_t k0 = 0; k0 < nOps; k0 += 64) {
-        const uint32_t k = k0 + lane; bool covered = false; uint32_t n = 0;
-        if (k < nOps) n = ydepth::opRef(ops[k], &covered);
-        uint32_t incl = n;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) { const uint32_t v = (uint32_t)__shfl_up((int)incl, s, 64); if ((int)lane >= s) incl += v; }
-        const uint32_t total = (uint32_t)__shfl((int)incl, 63, 64), excl = incl - n;
-        unsigned long long dels = __ballot(!covered && n != 0);
+        const OpChunk c = loadOpChunk(ops, nOps, k0, lane);
+        unsigned long long dels = __ballot(!c.covered && c.n != 0);
         while (dels) {                                                      // every D of the chunk ends the run before it
             const int l = __ffsll((long long)dels) - 1; dels &= dels - 1;
-            const uint32_t dOff = cur + (uint32_t)__shfl((int)excl, l, 64), dLen = (uint32_t)__shfl((int)n, l, 64);
+            const uint32_t dOff = cur + (uint32_t)__shfl((int)c.excl, l, 64), dLen = (uint32_t)__shfl((int)c.n, l, 64);
             ydepth::addRun(D.L, seq, runStart, dOff - runStart, lane, 64u, add);
             runStart = dOff + dLen;
         }
-        cur += total;
+        cur += c.total;
     }
     ydepth::addRun(D.L, seq, runStart, cur - runStart, lane, 64u, add);
 }

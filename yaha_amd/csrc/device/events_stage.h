@@ -15,7 +15,7 @@
 // bins goes straight to memory.)  At a bin of one base nothing can be combined and the branch -- the same on every lane -- is skipped.  The counts are exact
 // either way.
 #pragma once
-#include "common.h"
+#include "track_stage.h"
 #include "../events_core.h"
 
 struct EventsArgs {
@@ -39,9 +39,8 @@ __global__ void __launch_bounds__(256) k_event_clumps(EventsArgs E, const ygpu_o
         if (lane == 0 && outStart[lo] == w) atomicAdd(E.stats + 3, 1ull);
         return;
     }
-    int seq = -1; const int g = ydepth::gate(E.L, f.c, f.mapQuality, &seq);
-    if (lane == 0) atomicAdd(E.stats + g, 1ull);
-    if (g != ydepth::COUNTED) return;
+    int seq = -1;
+    if (!trackGate(E.L, f, E.stats, lane, &seq)) return;
     uint32_t *const ev = E.ev; const uint32_t nBins = E.nBins;
     auto add = [ev, nBins](uint32_t b, uint32_t ch, uint32_t n) { if (b < nBins && ch < (uint32_t)yevents::NCH) atomicAdd(ev + (size_t)b * yevents::NCH + ch, n); };
     if (lane == 0) {
@@ -51,13 +50,9 @@ __global__ void __launch_bounds__(256) k_event_clumps(EventsArgs E, const ygpu_o
     const uint32_t *ops = fOps + f.c.op_start; const uint32_t nOps = f.c.n_ops;
     uint32_t cur = f.c.sro;                                                 // (the same on every lane)
     for (uint32_t k0 = 0; k0 < nOps; k0 += 64) {
-        const uint32_t k = k0 + lane; const uint32_t op = k < nOps ? ops[k] : 0u, n = k < nOps ? yevents::opRef(op) : 0u;
-        uint32_t incl = n;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) { const uint32_t v = (uint32_t)__shfl_up((int)incl, s, 64); if ((int)lane >= s) incl += v; }
-        const uint32_t total = (uint32_t)__shfl((int)incl, 63, 64);
+        const OpChunk c = loadOpChunk(ops, nOps, k0, lane);
         yevents::OpEvents e; e.ch = 0; e.off = cur; e.len = 0;
-        if (k < nOps) e = yevents::opEvents(f.c, op, cur + incl - n);
+        if (c.k < nOps) e = yevents::opEvents(f.c, c.op, cur + c.excl);
         if (COMBINE) {
             // the op's share of its first bin, summed over the lanes of the same (channel, bin); the rest of a longer op goes its own way
             uint32_t bin0 = 0, n0 = 0;
@@ -78,6 +73,6 @@ __global__ void __launch_bounds__(256) k_event_clumps(EventsArgs E, const ygpu_o
             }
             if (e.len > n0) yevents::addSpan(E.L, seq, e.ch, e.off + n0, e.len - n0, add);
         } else yevents::addSpan(E.L, seq, e.ch, e.off, e.len, add);
-        cur += total;
+        cur += c.total;
     }
 }

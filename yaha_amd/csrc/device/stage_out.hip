@@ -8,25 +8,14 @@
 #include "events_stage.h"
 #include "junction_stage.h"
 #include <map>
+#include <tuple>
 
 extern "C" {
-int ygpu_collect(ygpu_ctx *ctx, ygpu_result_batch *out)
+int ygpu_collect(ygpu_ctx *ctx, ygpu_result_batch *out)                      // into the context's own vectors
 {
     if (!ctx || !out || ctx->stageDone < 3) return YGPU_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
-    const uint32_t n = ctx->nReads;
-    ctx->hClumpStart.assign(n + 1, 0); ctx->hClumps.resize(ctx->nOut); ctx->hOps.resize(ctx->nOutOps);
-    HIPCHK(hipMemcpyAsync(ctx->hClumpStart.data(), ctx->readStart.p, 4ull * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->nOut) HIPCHK(hipMemcpyAsync(ctx->hClumps.data(), ctx->outClumps2.p, sizeof(ygpu_clump) * (uint64_t)ctx->nOut, hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->nOutOps) HIPCHK(hipMemcpyAsync(ctx->hOps.data(), ctx->outOps.p, 4ull * ctx->nOutOps, hipMemcpyDeviceToHost, ctx->stream));
-    DevCounters dc; HIPCHK(hipMemcpyAsync(&dc, ctx->ctr.p, sizeof dc, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(streamSync(ctx));
-    { const unsigned long long dropped = dc.v[C_FRAGS];                      // dead single-hit fragments (each one a region of its own) that were counted, not written
-      dc.v[C_HITS] = ctx->nHits; dc.v[C_FRAGS] = ctx->nFrags + dropped; dc.v[C_REGIONS] = ctx->nRegions + dropped; }
-    memcpy(&ctx->hCounters, dc.v, sizeof(ygpu_counters));
-    out->n_reads = n; out->clump_start = ctx->hClumpStart.data(); out->clumps = ctx->hClumps.data(); out->ops = ctx->hOps.data();
-    out->n_clumps = ctx->nOut; out->n_ops = ctx->nOutOps; out->counters = ctx->hCounters;
-    return 0;
+    ctx->hClumpStart.assign(ctx->nReads + 1, 0); ctx->hClumps.resize(ctx->nOut); ctx->hOps.resize(ctx->nOutOps);
+    return ygpu_collect_into(ctx, ctx->hClumpStart.data(), ctx->hClumps.data(), ctx->hOps.data(), out);
 }
 
 int ygpu_result_size(ygpu_ctx *ctx, uint64_t *n_clumps, uint64_t *n_ops)
@@ -45,7 +34,7 @@ int ygpu_collect_into(ygpu_ctx *ctx, uint32_t *clump_start, ygpu_clump *clumps, 
     if (ctx->nOutOps) HIPCHK(hipMemcpyAsync(ops, ctx->outOps.p, 4ull * ctx->nOutOps, hipMemcpyDeviceToHost, ctx->stream));
     DevCounters dc; HIPCHK(hipMemcpyAsync(&dc, ctx->ctr.p, sizeof dc, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(streamSync(ctx));
-    { const unsigned long long dropped = dc.v[C_FRAGS];
+    { const unsigned long long dropped = dc.v[C_FRAGS];                      // dead single-hit fragments (each one a region of its own) that were counted, not written
       dc.v[C_HITS] = ctx->nHits; dc.v[C_FRAGS] = ctx->nFrags + dropped; dc.v[C_REGIONS] = ctx->nRegions + dropped; }
     memcpy(&ctx->hCounters, dc.v, sizeof(ygpu_counters));
     out->n_reads = n; out->clump_start = clump_start; out->clumps = clumps; out->ops = ops;
@@ -102,6 +91,42 @@ int ygpu_postfilter_snapshot(ygpu_ctx *ctx)
     ctx->snapHits = ctx->nHits; ctx->snapFrags = ctx->nFrags; ctx->snapRegions = ctx->nRegions;
     ctx->snapN = n; ctx->snapC = C; ctx->snapOps = O; ctx->oqDone = false;
     ctx->pfSnap.store(true);
+    return 0;
+}
+// A look-back of an exclusive sum on the post-filter's side gave up (CNT_SCANFAIL).  Not sticky: the flag and the look-back words -- stale tickets and statuses --
+// are made clean again for the next batch, as runTo does on its side; the call fails with `what`'s message.
+static int scanGaveUp(PfSide *ctx, const char *what)
+{
+    HIPCHK(hipMemsetAsync(ctx->counters.as<uint32_t>() + CNT_SCANFAIL, 0, 4, ctx->stream));
+    if (ctx->scanState.p) HIPCHK(hipMemsetAsync(ctx->scanState.p, 0, ctx->scanState.cap, ctx->stream));
+    HIPCHK(streamSync(ctx));
+    ctx->err = std::string(what) + ": a look-back of an exclusive sum gave up"; return YGPU_EINTERNAL;
+}
+static ydepth::Layout trackLayout(const TrackImage &T)
+{
+    return ydepth::Layout{T.seqStart.as<uint32_t>(), T.seqLength.as<uint32_t>(), T.binBase.as<uint32_t>(), (uint32_t)T.hSeqStart.size(), T.bin, T.minMapq};
+}
+// The binned tracks of the nClumps clumps just gathered -- the ones that get printed -- on the post-filter's stream, a wave a clump: the evidence track (the wave
+// finds its clump's read -- the query length of the right clip -- in oqOutStart; YGPU_EVENTS_DIRECT: every op's atomics without the combining in the wave, for
+// measurements; read at every call), then read depth and its count of the reads handed back.
+static int launchTracks(ygpu_ctx *full, uint32_t n, uint32_t nClumps)
+{
+    PfSide *ctx = &full->pf;
+    if (!nClumps) return 0;
+    const ygpu_out_clump *fClumps = full->oqFClumps.as<ygpu_out_clump>(); const uint32_t *fOps = full->oqFOps.as<uint32_t>();
+    const dim3 grid(gridFor((uint64_t)nClumps * 64, 256)), block(256);
+    if (const TrackImage *T = full->track[TRACK_EVENTS].get()) {
+        EventsArgs E; E.L = trackLayout(*T); E.minClip = T->minClip; E.ev = T->data.as<uint32_t>(); E.nBins = (uint32_t)T->nBins; E.stats = T->stats.as<unsigned long long>();
+        if (T->bin > 1 && getenv("YGPU_EVENTS_DIRECT") == nullptr)
+            KL(k_event_clumps<true>, grid, block, 0, ctx->stream, E, fClumps, fOps, full->oqOutStart.as<uint32_t>(), full->oqQlen.as<uint32_t>(), n, nClumps);
+        else
+            KL(k_event_clumps<false>, grid, block, 0, ctx->stream, E, fClumps, fOps, full->oqOutStart.as<uint32_t>(), full->oqQlen.as<uint32_t>(), n, nClumps);
+    }
+    if (const TrackImage *T = full->track[TRACK_DEPTH].get()) {
+        DepthArgs D; D.L = trackLayout(*T); D.cov = T->data.as<uint32_t>(); D.nBins = (uint32_t)T->nBins; D.stats = T->stats.as<unsigned long long>();
+        KL(k_depth_clumps, grid, block, 0, ctx->stream, D, fClumps, fOps, nClumps);
+        KL(k_depth_handed_back, dim3(gridFor(n, 256)), block, 0, ctx->stream, full->oqOutCnt.as<uint32_t>(), full->oqPrimCnt.as<uint32_t>(), n, D.stats);
+    }
     return 0;
 }
 static int postfilterBody(ygpu_ctx *full);
@@ -185,12 +210,7 @@ static int postfilterBody(ygpu_ctx *full)
     uint32_t tot[2] = {0, 0}, scanFail = 0;
     { const FetchPiece pc[3] = {{full->oqOutStart.as<uint32_t>() + n, &tot[0], 1}, {full->oqOpsStart.as<uint32_t>() + n, &tot[1], 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL,
         &scanFail, 1}}; rc = fetchMany(ctx, pc, 3); if (rc) return rc; }
-    if (scanFail) {      // (not sticky: the flag and the look-back words -- stale tickets and statuses -- are made clean again for the next batch, as runTo does on its side)
-        HIPCHK(hipMemsetAsync(ctx->counters.as<uint32_t>() + CNT_SCANFAIL, 0, 4, ctx->stream));
-        if (ctx->scanState.p) HIPCHK(hipMemsetAsync(ctx->scanState.p, 0, ctx->scanState.cap, ctx->stream));
-        HIPCHK(streamSync(ctx));
-        ctx->err = "post-filter: a look-back of an exclusive sum gave up"; return YGPU_EINTERNAL;
-    }
+    if (scanFail) return scanGaveUp(ctx, "post-filter");
     full->nFOut = tot[0]; full->nFOps = tot[1];
     ENSURE(full->oqFClumps, sizeof(ygpu_out_clump) * ((uint64_t)tot[0] + 1)); ENSURE(full->oqFOps, 4ull * ((uint64_t)tot[1] + 1));
     KL(k_oqc_gather, dim3(gridFor((uint64_t)n * 64, 256)), dim3(256), 0, ctx->stream, A, full->oqOutStart.as<uint32_t>(), full->oqOpsStart.as<uint32_t>(),
@@ -210,31 +230,8 @@ static int postfilterBody(ygpu_ctx *full)
         KL(k_junction_emit, grid, dim3(256), 0, ctx->stream, J);
         full->jnReads = n; full->jnDone = true;
     }
-    // the evidence track (-oev): mismatches, deleted bases, insertions and clipped ends of the clumps just gathered, a wave each, on this stage's stream; the
-    // wave finds its clump's read -- the query length of the right clip -- in oqOutStart.  (YGPU_EVENTS_DIRECT: every op's atomics without the combining in the
-    // wave, for measurements; read at every call.)
-    if (full->events && tot[0]) {
-        EventsImage &EI = *full->events; EventsArgs E;
-        E.L.seqStart = EI.seqStart.as<uint32_t>(); E.L.seqLength = EI.seqLength.as<uint32_t>(); E.L.binBase = EI.binBase.as<uint32_t>();
-        E.L.nSeqs = (uint32_t)EI.hSeqStart.size(); E.L.bin = EI.bin; E.L.minMapq = EI.minMapq; E.minClip = EI.minClip;
-        E.ev = EI.ev.as<uint32_t>(); E.nBins = (uint32_t)EI.nBins; E.stats = EI.stats.as<unsigned long long>();
-        const dim3 grid(gridFor((uint64_t)tot[0] * 64, 256));
-        if (EI.bin > 1 && getenv("YGPU_EVENTS_DIRECT") == nullptr)
-            KL(k_event_clumps<true>, grid, dim3(256), 0, ctx->stream, E, full->oqFClumps.as<ygpu_out_clump>(), full->oqFOps.as<uint32_t>(), full->oqOutStart.as<uint32_t>(),
-                full->oqQlen.as<uint32_t>(), n, tot[0]);
-        else
-            KL(k_event_clumps<false>, grid, dim3(256), 0, ctx->stream, E, full->oqFClumps.as<ygpu_out_clump>(), full->oqFOps.as<uint32_t>(), full->oqOutStart.as<uint32_t>(),
-                full->oqQlen.as<uint32_t>(), n, tot[0]);
-    }
-    // read depth (-ocov): the clumps just gathered are the ones that get printed -- a wave each adds what it covers to the image's array, on this stage's stream
-    if (full->depth && tot[0]) {
-        DepthImage &DI = *full->depth; DepthArgs D;
-        D.L.seqStart = DI.seqStart.as<uint32_t>(); D.L.seqLength = DI.seqLength.as<uint32_t>(); D.L.binBase = DI.binBase.as<uint32_t>();
-        D.L.nSeqs = (uint32_t)DI.hSeqStart.size(); D.L.bin = DI.bin; D.L.minMapq = DI.minMapq;
-        D.cov = DI.cov.as<uint32_t>(); D.nBins = (uint32_t)DI.nBins; D.stats = DI.stats.as<unsigned long long>();
-        KL(k_depth_clumps, dim3(gridFor((uint64_t)tot[0] * 64, 256)), dim3(256), 0, ctx->stream, D, full->oqFClumps.as<ygpu_out_clump>(), full->oqFOps.as<uint32_t>(), tot[0]);
-        KL(k_depth_handed_back, dim3(gridFor(n, 256)), dim3(256), 0, ctx->stream, full->oqOutCnt.as<uint32_t>(), full->oqPrimCnt.as<uint32_t>(), n, D.stats);
-    }
+    // the binned tracks that are enabled (-oev, -ocov), behind the junctions on this stage's stream
+    rc = launchTracks(full, n, tot[0]); if (rc) return rc;
     if (oqProf) {
         unsigned long long h[32 * YQ_NCLASS]; HIPCHK(hipMemcpyAsync(h, full->oqProf.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
         static const char *nm[7] = {"keys", "sort", "dup scan", "nodes+tables", "path walk", "successors", "finish"};
@@ -249,127 +246,87 @@ static int postfilterBody(ygpu_ctx *full)
     full->oqDone = true;
     return 0;
 }
-// ---- read depth along the reference (depth_stage.h; the contract is in ../depth_core.h) ---------------------------------------------------------------------
-// the coverage arrays of this process, by the image they belong to (the address of its bases on the device: what the contexts of an image share)
-static std::mutex gDepthMu;
-static std::map<std::pair<int, const void *>, std::weak_ptr<DepthImage>> gDepthImages;
+// ---- the binned tracks: read depth and the evidence track (depth_stage.h, events_stage.h; the contracts are in ../depth_core.h and ../events_core.h) ---------
+// What tells the two kinds apart outside their kernels: the entry points' names and the array's noun for messages, the option that makes the array smaller,
+// the words a bin takes, and whether a clip length belongs to the parameters.
+struct TrackKind { int kind; const char *enable, *size, *collect, *noun, *counted, *binOpt; uint32_t channels; bool hasClip; };
+static const TrackKind kDepthKind = {TRACK_DEPTH, "ygpu_depth_enable", "ygpu_depth_size", "ygpu_depth_collect", "coverage", "depth is", "-covbin", 1, false};
+static const TrackKind kEventsKind = {TRACK_EVENTS, "ygpu_events_enable", "ygpu_events_size", "ygpu_events_collect", "evidence", "the events are", "-evbin",
+    (uint32_t)yevents::NCH, true};
+// the arrays of this process, by kind and by the image they belong to (the address of its bases on the device: what the contexts of an image share)
+static std::mutex gTrackMu;
+static std::map<std::tuple<int, int, const void *>, std::weak_ptr<TrackImage>> gTrackImages;
+
+static int trackEnable(ygpu_ctx *ctx, const TrackKind &K, uint32_t bin, uint32_t minMapq, uint32_t minClip, uint32_t nSeqs, const uint32_t *seqStart, const uint32_t *seqLength)
+{
+    if (!ctx || !ctx->stream) return YGPU_EINVAL;
+    const std::string who = std::string(K.enable) + ": ";
+    if (!ctx->oqSet) { ctx->err = who + "ygpu_set_postfilter has not been called on this context (" + K.counted + " counted behind the post-filter)"; return YGPU_EINVAL; }
+    if (bin < 1 || (K.hasClip && minClip < 1) || !nSeqs || !seqStart || !seqLength) {
+        ctx->err = who + (K.hasClip ? "bad bin size, clip length or sequence table" : "bad bin size or sequence table"); return YGPU_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    std::lock_guard<std::mutex> lk(gTrackMu);
+    const std::tuple<int, int, const void *> key(K.kind, ctx->device, ctx->dBases.p);
+    if (std::shared_ptr<TrackImage> have = gTrackImages[key].lock()) {      // a sibling enabled it: the same array, if the same track is asked for
+        if (have->bin != bin || have->minMapq != minMapq || have->minClip != minClip || have->hSeqStart.size() != nSeqs
+            || memcmp(have->hSeqStart.data(), seqStart, 4ull * nSeqs) != 0 || memcmp(have->hSeqLength.data(), seqLength, 4ull * nSeqs) != 0) {
+            ctx->err = who + "the image's " + K.noun + " array was enabled with other parameters"; return YGPU_EINVAL; }
+        ctx->track[K.kind] = have; return 0;
+    }
+    std::shared_ptr<TrackImage> T(new TrackImage); T->device = ctx->device; T->channels = K.channels; T->bin = bin; T->minMapq = minMapq; T->minClip = minClip;
+    T->hSeqStart.assign(seqStart, seqStart + nSeqs); T->hSeqLength.assign(seqLength, seqLength + nSeqs);
+    std::vector<uint32_t> binBase(nSeqs + 1);
+    if (!ydepth::layoutBins(seqLength, nSeqs, bin, binBase.data(), &T->nBins) || T->nBins == 0) { ctx->err = who + "the bins do not fit 32 bits"; return YGPU_EINVAL; }
+    const uint64_t bytes = 4ull * K.channels * T->nBins;
+    if (T->data.ensureExact(bytes)) {                                       // (exact: a growth margin on 12 GB is 3 GB)
+        (void)hipGetLastError(); size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) != hipSuccess) { fb = 0; (void)hipGetLastError(); }
+        char perBin[32] = ""; if (K.channels > 1) snprintf(perBin, sizeof perBin, " (%u bytes a bin)", 4u * K.channels);
+        char m[256]; snprintf(m, sizeof m, "%sno room on device %d for the %s array: %.2f GB for %llu bins of %u bases%s, %.2f GB free (a larger %s needs less)", who.c_str(),
+            ctx->device, K.noun, bytes / 1e9, (unsigned long long)T->nBins, bin, perBin, fb / 1e9, K.binOpt);
+        ctx->err = m; return YGPU_ENOMEM;
+    }
+    if (T->stats.ensure(64) || T->seqStart.ensure(4ull * nSeqs) || T->seqLength.ensure(4ull * nSeqs) || T->binBase.ensure(4ull * (nSeqs + 1))) {
+        (void)hipGetLastError(); ctx->err = who + "hipMalloc failed"; return YGPU_ENOMEM; }
+    HIPCHK(hipMemsetAsync(T->data.p, 0, bytes, ctx->stream)); HIPCHK(hipMemsetAsync(T->stats.p, 0, 64, ctx->stream));
+    HIPCHK(hipMemcpyAsync(T->seqStart.p, seqStart, 4ull * nSeqs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(T->seqLength.p, seqLength, 4ull * nSeqs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(T->binBase.p, binBase.data(), 4ull * (nSeqs + 1), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(streamSync(ctx));
+    gTrackImages[key] = T; ctx->track[K.kind] = T;
+    return 0;
+}
+static int trackSize(ygpu_ctx *ctx, const TrackKind &K, uint64_t *n_bins)
+{
+    if (!ctx || !n_bins) return YGPU_EINVAL;
+    if (!ctx->track[K.kind]) { ctx->err = std::string(K.size) + ": " + K.enable + " has not been called on this context"; return YGPU_EINVAL; }
+    *n_bins = ctx->track[K.kind]->nBins; return 0;
+}
+// The image's array as it stands: every filter stage queued on the device so far -- this context's and its siblings' -- has finished when the copy is taken.
+static int trackCollect(ygpu_ctx *ctx, const TrackKind &K, uint32_t *words, uint64_t stats[4])
+{
+    if (!ctx || !ctx->stream) return YGPU_EINVAL;
+    if (!ctx->track[K.kind]) { ctx->err = std::string(K.collect) + ": " + K.enable + " has not been called on this context"; return YGPU_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipDeviceSynchronize());
+    const TrackImage &T = *ctx->track[K.kind];
+    if (words) HIPCHK(hipMemcpy(words, T.data.p, 4ull * T.channels * T.nBins, hipMemcpyDeviceToHost));
+    if (stats) { unsigned long long h[4]; HIPCHK(hipMemcpy(h, T.stats.p, sizeof h, hipMemcpyDeviceToHost)); for (int k = 0; k < 4; k++) stats[k] = h[k]; }
+    return 0;
+}
 int ygpu_depth_enable(ygpu_ctx *ctx, const ygpu_depth_params *p)
 {
-    if (!ctx || !ctx->stream || !p) return YGPU_EINVAL;
-    if (!ctx->oqSet) { ctx->err = "ygpu_depth_enable: ygpu_set_postfilter has not been called on this context (depth is counted behind the post-filter)"; return YGPU_EINVAL; }
-    if (p->bin < 1 || !p->n_seqs || !p->seq_start || !p->seq_length) { ctx->err = "ygpu_depth_enable: bad bin size or sequence table";
-        return YGPU_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
-    std::lock_guard<std::mutex> lk(gDepthMu);
-    const std::pair<int, const void *> key(ctx->device, ctx->dBases.p);
-    if (std::shared_ptr<DepthImage> have = gDepthImages[key].lock()) {      // a sibling enabled it: the same array, if the same track is asked for
-        if (have->bin != p->bin || have->minMapq != p->min_mapq || have->hSeqStart.size() != p->n_seqs
-            || memcmp(have->hSeqStart.data(), p->seq_start, 4ull * p->n_seqs) != 0 || memcmp(have->hSeqLength.data(), p->seq_length, 4ull * p->n_seqs) != 0) {
-            ctx->err = "ygpu_depth_enable: the image's coverage array was enabled with other parameters"; return YGPU_EINVAL; }
-        ctx->depth = have; return 0;
-    }
-    std::shared_ptr<DepthImage> DI(new DepthImage); DI->device = ctx->device; DI->bin = p->bin; DI->minMapq = p->min_mapq;
-    DI->hSeqStart.assign(p->seq_start, p->seq_start + p->n_seqs); DI->hSeqLength.assign(p->seq_length, p->seq_length + p->n_seqs);
-    std::vector<uint32_t> binBase(p->n_seqs + 1);
-    if (!ydepth::layoutBins(p->seq_length, p->n_seqs, p->bin, binBase.data(), &DI->nBins) || DI->nBins == 0) { ctx->err = "ygpu_depth_enable: the bins do not fit 32 bits";
-        return YGPU_EINVAL; }
-    // (exact: a growth margin on 12 GB is 3 GB)
-    if (DI->cov.ensureExact(4ull * DI->nBins)) {
-        (void)hipGetLastError(); size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) != hipSuccess) { fb = 0; (void)hipGetLastError(); }
-        char m[256]; snprintf(m, sizeof m, "ygpu_depth_enable: no room on device %d for the coverage array: %.2f GB for %llu bins of %u bases, %.2f GB free "
-            "(a larger -covbin needs less)", ctx->device, 4.0 * DI->nBins / 1e9, (unsigned long long)DI->nBins, p->bin, fb / 1e9);
-        ctx->err = m; return YGPU_ENOMEM;
-    }
-    if (DI->stats.ensure(64) || DI->seqStart.ensure(4ull * p->n_seqs) || DI->seqLength.ensure(4ull * p->n_seqs) || DI->binBase.ensure(4ull * (p->n_seqs + 1))) {
-        (void)hipGetLastError(); ctx->err = "ygpu_depth_enable: hipMalloc failed"; return YGPU_ENOMEM; }
-    HIPCHK(hipMemsetAsync(DI->cov.p, 0, 4ull * DI->nBins, ctx->stream)); HIPCHK(hipMemsetAsync(DI->stats.p, 0, 64, ctx->stream));
-    HIPCHK(hipMemcpyAsync(DI->seqStart.p, p->seq_start, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(DI->seqLength.p, p->seq_length, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(DI->binBase.p, binBase.data(), 4ull * (p->n_seqs + 1), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(streamSync(ctx));
-    gDepthImages[key] = DI; ctx->depth = DI;
-    return 0;
+    return p ? trackEnable(ctx, kDepthKind, p->bin, p->min_mapq, 0, p->n_seqs, p->seq_start, p->seq_length) : YGPU_EINVAL;
 }
-int ygpu_depth_size(ygpu_ctx *ctx, uint64_t *n_bins)
-{
-    if (!ctx || !n_bins) return YGPU_EINVAL;
-    if (!ctx->depth) { ctx->err = "ygpu_depth_size: ygpu_depth_enable has not been called on this context"; return YGPU_EINVAL; }
-    *n_bins = ctx->depth->nBins; return 0;
-}
-// The image's array as it stands: every filter stage queued on the device so far -- this context's and its siblings' -- has finished when the copy is taken.
-int ygpu_depth_collect(ygpu_ctx *ctx, uint32_t *bins, uint64_t stats[4])
-{
-    if (!ctx || !ctx->stream) return YGPU_EINVAL;
-    if (!ctx->depth) { ctx->err = "ygpu_depth_collect: ygpu_depth_enable has not been called on this context"; return YGPU_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipDeviceSynchronize());
-    DepthImage &DI = *ctx->depth;
-    if (bins) HIPCHK(hipMemcpy(bins, DI.cov.p, 4ull * DI.nBins, hipMemcpyDeviceToHost));
-    if (stats) { unsigned long long h[4]; HIPCHK(hipMemcpy(h, DI.stats.p, sizeof h, hipMemcpyDeviceToHost)); for (int k = 0; k < 4; k++) stats[k] = h[k]; }
-    return 0;
-}
-// ---- the evidence track (events_stage.h; the contract is in ../events_core.h) -----------------------------------------------------------------------------
-// the arrays of this process by index image, as the coverage arrays above
-static std::mutex gEventsMu;
-static std::map<std::pair<int, const void *>, std::weak_ptr<EventsImage>> gEventsImages;
+int ygpu_depth_size(ygpu_ctx *ctx, uint64_t *n_bins) { return trackSize(ctx, kDepthKind, n_bins); }
+int ygpu_depth_collect(ygpu_ctx *ctx, uint32_t *bins, uint64_t stats[4]) { return trackCollect(ctx, kDepthKind, bins, stats); }
 int ygpu_events_enable(ygpu_ctx *ctx, const ygpu_events_params *p)
 {
-    if (!ctx || !ctx->stream || !p) return YGPU_EINVAL;
-    if (!ctx->oqSet) { ctx->err = "ygpu_events_enable: ygpu_set_postfilter has not been called on this context (the events are counted behind the post-filter)";
-        return YGPU_EINVAL; }
-    if (p->bin < 1 || p->min_clip < 1 || !p->n_seqs || !p->seq_start || !p->seq_length) { ctx->err = "ygpu_events_enable: bad bin size, clip length or sequence table";
-        return YGPU_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
-    std::lock_guard<std::mutex> lk(gEventsMu);
-    const std::pair<int, const void *> key(ctx->device, ctx->dBases.p);
-    if (std::shared_ptr<EventsImage> have = gEventsImages[key].lock()) {    // a sibling enabled it: the same array, if the same track is asked for
-        if (have->bin != p->bin || have->minMapq != p->min_mapq || have->minClip != p->min_clip || have->hSeqStart.size() != p->n_seqs
-            || memcmp(have->hSeqStart.data(), p->seq_start, 4ull * p->n_seqs) != 0 || memcmp(have->hSeqLength.data(), p->seq_length, 4ull * p->n_seqs) != 0) {
-            ctx->err = "ygpu_events_enable: the image's evidence array was enabled with other parameters"; return YGPU_EINVAL; }
-        ctx->events = have; return 0;
-    }
-    std::shared_ptr<EventsImage> EI(new EventsImage); EI->device = ctx->device; EI->bin = p->bin; EI->minMapq = p->min_mapq; EI->minClip = p->min_clip;
-    EI->hSeqStart.assign(p->seq_start, p->seq_start + p->n_seqs); EI->hSeqLength.assign(p->seq_length, p->seq_length + p->n_seqs);
-    std::vector<uint32_t> binBase(p->n_seqs + 1);
-    if (!ydepth::layoutBins(p->seq_length, p->n_seqs, p->bin, binBase.data(), &EI->nBins) || EI->nBins == 0) { ctx->err = "ygpu_events_enable: the bins do not fit 32 bits";
-        return YGPU_EINVAL; }
-    const uint64_t bytes = 4ull * yevents::NCH * EI->nBins;
-    if (EI->ev.ensureExact(bytes)) {
-        (void)hipGetLastError(); size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) != hipSuccess) { fb = 0; (void)hipGetLastError(); }
-        char m[256]; snprintf(m, sizeof m, "ygpu_events_enable: no room on device %d for the evidence array: %.2f GB for %llu bins of %u bases (20 bytes a bin), %.2f GB free "
-            "(a larger -evbin needs less)", ctx->device, bytes / 1e9, (unsigned long long)EI->nBins, p->bin, fb / 1e9);
-        ctx->err = m; return YGPU_ENOMEM;
-    }
-    if (EI->stats.ensure(64) || EI->seqStart.ensure(4ull * p->n_seqs) || EI->seqLength.ensure(4ull * p->n_seqs) || EI->binBase.ensure(4ull * (p->n_seqs + 1))) {
-        (void)hipGetLastError(); ctx->err = "ygpu_events_enable: hipMalloc failed"; return YGPU_ENOMEM; }
-    HIPCHK(hipMemsetAsync(EI->ev.p, 0, bytes, ctx->stream)); HIPCHK(hipMemsetAsync(EI->stats.p, 0, 64, ctx->stream));
-    HIPCHK(hipMemcpyAsync(EI->seqStart.p, p->seq_start, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(EI->seqLength.p, p->seq_length, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(EI->binBase.p, binBase.data(), 4ull * (p->n_seqs + 1), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(streamSync(ctx));
-    gEventsImages[key] = EI; ctx->events = EI;
-    return 0;
+    return p ? trackEnable(ctx, kEventsKind, p->bin, p->min_mapq, p->min_clip, p->n_seqs, p->seq_start, p->seq_length) : YGPU_EINVAL;
 }
-int ygpu_events_size(ygpu_ctx *ctx, uint64_t *n_bins)
-{
-    if (!ctx || !n_bins) return YGPU_EINVAL;
-    if (!ctx->events) { ctx->err = "ygpu_events_size: ygpu_events_enable has not been called on this context"; return YGPU_EINVAL; }
-    *n_bins = ctx->events->nBins; return 0;
-}
-// The image's array as it stands: every filter stage queued on the device so far -- this context's and its siblings' -- has finished when the copy is taken.
-int ygpu_events_collect(ygpu_ctx *ctx, uint32_t *counts, uint64_t stats[4])
-{
-    if (!ctx || !ctx->stream) return YGPU_EINVAL;
-    if (!ctx->events) { ctx->err = "ygpu_events_collect: ygpu_events_enable has not been called on this context"; return YGPU_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipDeviceSynchronize());
-    EventsImage &EI = *ctx->events;
-    if (counts) HIPCHK(hipMemcpy(counts, EI.ev.p, 4ull * yevents::NCH * EI.nBins, hipMemcpyDeviceToHost));
-    if (stats) { unsigned long long h[4]; HIPCHK(hipMemcpy(h, EI.stats.p, sizeof h, hipMemcpyDeviceToHost)); for (int k = 0; k < 4; k++) stats[k] = h[k]; }
-    return 0;
-}
+int ygpu_events_size(ygpu_ctx *ctx, uint64_t *n_bins) { return trackSize(ctx, kEventsKind, n_bins); }
+int ygpu_events_collect(ygpu_ctx *ctx, uint32_t *counts, uint64_t stats[4]) { return trackCollect(ctx, kEventsKind, counts, stats); }
 // ---- split-read junctions (junction_stage.h; the contract is in ../junction_core.h) --------------------------------------------------------------------------
-// Per batch and per context, unlike the two tracks above: the junctions of the batch the context's last ygpu_postfilter filtered.
+// Per batch and per context, unlike the binned tracks above: the junctions of the batch the context's last ygpu_postfilter filtered.
 int ygpu_junctions_enable(ygpu_ctx *ctx, const ygpu_junction_params *p)
 {
     if (!ctx || !ctx->stream || !p) return YGPU_EINVAL;
@@ -397,12 +354,7 @@ static int junctionsTotal(ygpu_ctx *full, const char *who)
     uint32_t tot = 0, scanFail = 0;
     { const FetchPiece pc[2] = {{full->jnStart.as<uint32_t>() + full->jnReads, &tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1}};
       const int rc = fetchMany(ctx, pc, 2); if (rc) return rc; }
-    if (scanFail) {                                                          // (made clean again for the next batch, as ygpu_postfilter does)
-        HIPCHK(hipMemsetAsync(ctx->counters.as<uint32_t>() + CNT_SCANFAIL, 0, 4, ctx->stream));
-        if (ctx->scanState.p) HIPCHK(hipMemsetAsync(ctx->scanState.p, 0, ctx->scanState.cap, ctx->stream));
-        HIPCHK(streamSync(ctx));
-        ctx->err = "junctions: a look-back of an exclusive sum gave up"; return YGPU_EINTERNAL;
-    }
+    if (scanFail) return scanGaveUp(ctx, "junctions");
     tlsPfFailed = nullptr;
     if ((uint64_t)tot * sizeof(ygpu_junction) > full->jnOut.cap) { full->err = std::string(who) + ": more junctions than the batch has clumps"; return YGPU_EINTERNAL; }
     full->jnTotal = tot; full->jnHaveTotal = true;

@@ -30,11 +30,7 @@ YDP_FN uint32_t binOf(const ydepth::Layout &L, int seq, uint32_t off)
     return L.binBase[seq] + (off >= s ? off - s : 0u) / L.bin;
 }
 // reference bases an op consumes (M, R, D)
-YDP_FN uint32_t opRef(uint32_t op)
-{
-    const char code = YGPU_OP_CODE(op);
-    return (code == 'M' || code == 'R' || code == 'D') ? YGPU_OP_LEN(op) : 0u;
-}
+YDP_FN uint32_t opRef(uint32_t op) { bool covered; return ydepth::opRef(op, &covered); }
 // What an op emits when the walk stands at reference offset cur: one event of channel ch for each of the bases [off, off + len); len 0: nothing (M, clips).
 // An I is one event at the next reference base, kept inside the record.
 struct OpEvents { uint32_t ch, off, len; };

@@ -22,13 +22,11 @@ using namespace yaha;
 
 struct yaha_session {
     Args args; Genome genome; IndexFile index; ReadReader reader; std::string err, header; Text text;
-    std::vector<uint32_t> evSeqStart, evSeqLen;                      // what yaha_session_events_params points into
-    std::vector<uint32_t> jnSeqStart, jnSeqLen;                      // what yaha_session_junction_params points into
-    std::vector<uint32_t> pfThr, pfSeqStart, pfSeqLen;               // what yaha_session_postfilter_params points into
+    std::vector<uint32_t> seqStart, seqLen;                          // the genome's sequence table (sessionLoad): what every yaha_session_*_params points into
+    std::vector<uint32_t> pfThr;                                     // the break point table yaha_session_postfilter_params points into
     std::vector<Read> reads; std::vector<uint8_t> codes; std::vector<uint64_t> offsets;
     bool readerOpen = false;
-    DepthTrack *depth = nullptr;                                     // -ocov (the command line): the formatters add the records the device did not count
-    EventsTrack *events = nullptr;                                   // -oev: the same for the evidence track
+    std::vector<BinnedTrack *> tracks;                               // -ocov, -oev (the command line): the formatters add the records the device did not count
     // -obp: the formatters make the junctions of the reads the device did not (junctions.cpp) into the batch's own list; their counts of the batch
     const JunctionTrack *junctions = nullptr; std::vector<ygpu_junction> *jnOut = nullptr; uint64_t jnReads = 0, jnSkipped = 0;
 };
@@ -111,6 +109,7 @@ static bool sessionLoad(yaha_session *s)
 {
     Args &a = s->args;
     if (!loadNib2(a.gfileName.c_str(), s->genome, s->err)) return false;
+    for (auto &sq : s->genome.seqs) { s->seqStart.push_back(sq.start); s->seqLen.push_back(sq.length); }
     if (!loadIndex(a.xfileName.c_str(), s->index, s->err)) return false;
     a.wordLen = s->index.wordLen;                                            // Query.c:603-610
     if (s->index.maxHits < a.maxHits) {
@@ -134,23 +133,30 @@ static void hostJunctions(yaha_session *s, uint32_t i, const OutClump *recs, uin
     if (s->junctions->addRead(recs, n, s->reads[i].len(), i, *s->jnOut, &skipped)) s->jnReads++;
     s->jnSkipped += skipped;
 }
+// What of a batch was counted on the device, as a bit mask: bit t = the session's binned track t; the batch's junctions were made there as well
+enum : unsigned { kJunctionsOnDevice = 1u << 31 };
+// one record of read i: its text, and its share of every binned track the device did not count it for
+static inline void emitRecord(yaha_session *s, uint32_t i, const OutClump &o, int primaryCount, Text &text, unsigned onDevice = 0)
+{
+    printClump(s->args, s->genome, s->reads[i], o, primaryCount, text);
+    for (size_t t = 0; t < s->tracks.size(); t++) if (!(onDevice >> t & 1u)) s->tracks[t]->add(o, s->reads[i].len());
+}
 static void formatRange(yaha_session *s, const ygpu_result_batch *r, uint32_t i0, uint32_t i1, Text &text, std::vector<OutClump> &oc)
 {
     const Args &a = s->args;
     for (uint32_t i = i0; i < i1; i++) {
         uint32_t c0 = r->clump_start[i], c1 = r->clump_start[i + 1]; int primaryCount = 0;
         postFilter(a, s->genome, s->reads[i], r->clumps + c0, c1 - c0, r->ops, oc, primaryCount);
-        for (auto &o : oc) { printClump(a, s->genome, s->reads[i], o, primaryCount, text); if (s->depth) s->depth->add(o); if (s->events) s->events->add(o, s->reads[i].len()); }
+        for (auto &o : oc) emitRecord(s, i, o, primaryCount, text);
         if (s->junctions && s->jnOut) hostJunctions(s, i, oc.data(), (uint32_t)oc.size());
     }
 }
 // SAM text of a batch whose post-filter ran on the device (ygpu_postfilter): the clumps arrive in print order with the filter's fields set
-// (depthOnDevice / eventsOnDevice / junctionsOnDevice: the device stage counted the batch's read depth / evidence track, made its junctions as well -- all but
-// those of the reads it handed back unfiltered)
-static void formatFiltered(yaha_session *s, const ygpu_filtered_batch *r, Text &text, bool depthOnDevice = false, bool eventsOnDevice = false, bool junctionsOnDevice = false)
+// (onDevice: what the device stage counted of the batch's binned tracks, whether it made its junctions as well -- all but those of the reads it handed back unfiltered)
+static void formatFiltered(yaha_session *s, const ygpu_filtered_batch *r, Text &text, unsigned onDevice = 0)
 {
     const Args &a = s->args; text.clear();
-    const bool hostJn = s->junctions && s->jnOut;
+    const bool hostJn = s->junctions && s->jnOut, junctionsOnDevice = (onDevice & kJunctionsOnDevice) != 0;
     std::vector<ygpu_clump> raw; std::vector<OutClump> oc;
     for (uint32_t i = 0; i < r->n_reads; i++) {
         const uint32_t k0 = r->clump_start[i], k1 = r->clump_start[i + 1];
@@ -159,8 +165,7 @@ static void formatFiltered(yaha_session *s, const ygpu_filtered_batch *r, Text &
             raw.resize(k1 - k0); for (uint32_t k = k0; k < k1; k++) raw[k - k0] = r->clumps[k].c;
             int primaryCount = 0;
             postFilter(a, s->genome, s->reads[i], raw.data(), k1 - k0, r->ops, oc, primaryCount);
-            for (auto &o : oc) { printClump(a, s->genome, s->reads[i], o, primaryCount, text); if (s->depth) s->depth->add(o);
-                if (s->events) s->events->add(o, s->reads[i].len()); }
+            for (auto &o : oc) emitRecord(s, i, o, primaryCount, text);
             if (hostJn) hostJunctions(s, i, oc.data(), (uint32_t)oc.size());
             continue;
         }
@@ -169,9 +174,7 @@ static void formatFiltered(yaha_session *s, const ygpu_filtered_batch *r, Text &
             const ygpu_out_clump &f = r->clumps[k];
             OutClump o; o.c = f.c; o.ops = r->ops + f.c.op_start; o.status = f.status; o.mapQuality = f.mapQuality; o.numSecondaries = f.numSecondaries;
                 o.matchedPrimary = f.matchedPrimary;
-            printClump(a, s->genome, s->reads[i], o, (int)f.primaryCount, text);
-            if (s->depth && !depthOnDevice) s->depth->add(o);
-            if (s->events && !eventsOnDevice) s->events->add(o, s->reads[i].len());
+            emitRecord(s, i, o, (int)f.primaryCount, text, onDevice);
             if (hostJn && !junctionsOnDevice) oc.push_back(o);
         }
         if (hostJn && !junctionsOnDevice && k1 - k0 >= 2) hostJunctions(s, i, oc.data(), (uint32_t)oc.size());
@@ -233,12 +236,25 @@ int runQueries(Args &a, FILE *log)
     Args &A = S->args;
     FILE *out = (A.ofileName == "stdout") ? stdout : fopen(A.ofileName.c_str(), "w");
     if (!out) { fprintf(log, "Failure to open output file: %s.\n", A.ofileName.c_str()); return 1; }
-    // -ocov: the host's coverage array (depth.cpp); the device stage behind the post-filter feeds one of its own per index image, merged at the end
-    std::unique_ptr<DepthTrack> depth;
-    if (A.haveCov) { depth.reset(new DepthTrack); if (!depth->init(S->genome, A.covBin, A.covMinQ, S->err)) { fprintf(log, "%s\n", S->err.c_str()); return 1; } }
-    // -oev: the same for the evidence track (events.cpp)
-    std::unique_ptr<EventsTrack> events;
-    if (A.haveEv) { events.reset(new EventsTrack); if (!events->init(S->genome, A.evBin, A.evMinQ, A.evMinClip, S->err)) { fprintf(log, "%s\n", S->err.c_str()); return 1; } }
+    // -gpus N devices x -ctx M contexts per device (default 3 -- four contexts of ~60 GB beside the image leave a later, heavier batch no memory to grow into: measured slower;
+    // while one context's batch is in a latency-bound device stage the others'
+    // batches compute).  Contexts of one device share its index image.
+    const int perDev = std::max(1, A.ctxPerGpu), nDev = std::max(1, A.gpus), ngpu = nDev * perDev;
+    // The run's binned tracks (depth.cpp, events.cpp), one table entry each: the host's array, what it is made with, its file, the switch that keeps it on the
+    // host, its keys of the stats line.  The device stage behind the post-filter feeds an array of its own per index image, enabled by every context of the image
+    // (the first makes it) and merged at the end: feeder[k] = 1 + a context of device k that feeds it.  Without the entry points (a build without them), with the
+    // switch set, or when the stage is refused, the formatters count everything.  Track t is bit t of a batch's onDevice mask.
+    struct TrackRun { std::unique_ptr<BinnedTrack> track; int binBases, minQ; const std::string *file; const char *hostSwitch, *statsFmt; bool onDevice;
+                      std::vector<std::atomic<int>> feeder; };
+    std::vector<TrackRun> tracks;
+    if (A.haveCov) tracks.push_back(TrackRun{std::unique_ptr<BinnedTrack>(new DepthTrack), A.covBin, A.covMinQ, &A.covFileName, "YAHA_HOST_DEPTH",
+        ", \"depth_bins\": %llu, \"depth_device_records\": %llu, \"depth_host_records\": %llu, \"depth_covered_bases\": %llu", false, {}});
+    if (A.haveEv) tracks.push_back(TrackRun{std::unique_ptr<BinnedTrack>(new EventsTrack(A.evMinClip)), A.evBin, A.evMinQ, &A.evFileName, "YAHA_HOST_EVENTS",
+        ", \"events_bins\": %llu, \"events_device_records\": %llu, \"events_host_records\": %llu, \"events_counted\": %llu", false, {}});
+    for (auto &T : tracks) {
+        if (!T.track->init(S->genome, T.binBases, T.minQ, S->err)) { fprintf(log, "%s\n", S->err.c_str()); return 1; }
+        T.feeder = std::vector<std::atomic<int>>(nDev); for (auto &x : T.feeder) x = 0;
+    }
     // -obp: the run's junctions (junctions.cpp); a batch's are made on the device behind its post-filter and travel with it
     std::unique_ptr<JunctionTrack> junctions;
     if (A.haveBp) { junctions.reset(new JunctionTrack); junctions->init(S->genome, A.bpMinQ, A.bpWindow); }
@@ -246,10 +262,6 @@ int runQueries(Args &a, FILE *log)
     if (fputs(S->header.c_str(), out) < 0) { fprintf(log, "Failure writing the output file.\n"); return 1; }
     ygpu_params P; paramsFromArgs(A, P);
     ygpu_index_view V; yaha_session_index_view(S.get(), &V);
-    // -gpus N devices x -ctx M contexts per device (default 3 -- four contexts of ~60 GB beside the image leave a later, heavier batch no memory to grow into: measured slower;
-    // while one context's batch is in a latency-bound device stage the others'
-    // batches compute).  Contexts of one device share its index image.
-    const int perDev = std::max(1, A.ctxPerGpu), nDev = std::max(1, A.gpus), ngpu = nDev * perDev;
     std::vector<ygpu_ctx *> ctx(ngpu, nullptr);
     // Six stages, batches handed over through bounded queues, a ticket ordering the output (= the reference's -t 1 order):
     //   splitter   (1 thread)          record boundaries of the memory-mapped / block-read input (memchr; reader.cpp) -- the only serial part;
@@ -277,9 +289,9 @@ int runQueries(Args &a, FILE *log)
         }
     };
     struct Batch { uint64_t ticket = 0; std::vector<Span> spans; std::vector<Read> reads; size_t nReads = 0; std::vector<uint8_t> codes; std::vector<uint64_t> offsets;
-                   ResBuf clumpStart, ops, clumps; uint64_t nClumps = 0, nOps = 0; bool filtered = false, depthOnDevice = false, eventsOnDevice = false; Text text;
+                   ResBuf clumpStart, ops, clumps; uint64_t nClumps = 0, nOps = 0; bool filtered = false; unsigned onDevice = 0; Text text;
                    // -obp: the junctions the device made of the batch and its statistics; the ones the formatter made, and its counts
-                   bool junctionsOnDevice = false; std::vector<ygpu_junction> jnDev, jnHost; uint64_t jnDevStats[4] = {0, 0, 0, 0}, jnHostReads = 0, jnHostSkipped = 0;
+                   std::vector<ygpu_junction> jnDev, jnHost; uint64_t jnDevStats[4] = {0, 0, 0, 0}, jnHostReads = 0, jnHostSkipped = 0;
                    double tRead = 0, tDev = 0, tFmt = 0; };
     typedef std::unique_ptr<Batch> BatchP;
     struct Pool { std::mutex mu; std::vector<BatchP> free; BatchP get() { { std::lock_guard<std::mutex> lk(mu); if (!free.empty()) { BatchP b = std::move(free.back());
@@ -336,28 +348,21 @@ int runQueries(Args &a, FILE *log)
     // The post-filter (OQC, filter by similarity, mapping quality) runs on the device behind the hot path (ygpu_postfilter; the same routine as the host's,
     // oqc_core.h): the results that cross PCIe and reach the formatters are the clumps that get printed.  The host filter remains for -OQC N (duplicate
     // removal only), for break point costs that are no step function, and on request (-dpf N, YAHA_HOST_OQC=1).
-    yoqc::Params oqP; std::vector<uint32_t> oqThr, oqSeqStart, oqSeqLen; oqcParamsFromArgs(A, oqP, oqThr);
-    for (auto &sq : S->genome.seqs) { oqSeqStart.push_back(sq.start); oqSeqLen.push_back(sq.length); }
+    yoqc::Params oqP; std::vector<uint32_t> oqThr; oqcParamsFromArgs(A, oqP, oqThr);
     // (-MNO below 1: the graph's successor test then also lets a node relax itself and nodes before it, which the device stage's one-successor-per-lane step does not order
     // the way the sequential loop does, GraphPath.cpp:633-700 -- those runs keep the host filter, as ygpu_set_postfilter insists)
     const bool deviceFilter = A.OQC && A.devicePostFilter && oqP.bppN >= 0 && oqP.minNonOverlap >= 1 && getenv("YAHA_HOST_OQC") == nullptr;
     ygpu_postfilter_params PF; memset(&PF, 0, sizeof PF);
     PF.minNonOverlap = oqP.minNonOverlap; PF.BPCost = oqP.BPCost; PF.maxBPLog = oqP.maxBPLog; PF.FBS = oqP.FBS; PF.FBS_PSLength = oqP.FBS_PSLength;
         PF.FBS_PSScore = oqP.FBS_PSScore;
-    PF.bppVmin = oqP.bppVmin; PF.bppN = std::max(0, oqP.bppN); PF.bppThr = oqThr.data(); PF.n_seqs = (uint32_t)oqSeqStart.size(); PF.seq_start = oqSeqStart.data();
-        PF.seq_length = oqSeqLen.data();
+    PF.bppVmin = oqP.bppVmin; PF.bppN = std::max(0, oqP.bppN); PF.bppThr = oqThr.data(); PF.n_seqs = (uint32_t)S->seqStart.size(); PF.seq_start = S->seqStart.data();
+        PF.seq_length = S->seqLen.data();
     // ready: 0 = image not there yet, 1 = there, -1 = failed
     struct Warm { std::mutex mu, first; std::condition_variable cv; int firstRunning = 0; int ready = 0; uint64_t footprint = 0;
         bool claimed = false, measured = false, haveProfile = false; ygpu_arena_profile profile; };
     std::vector<std::unique_ptr<Warm>> warm; for (int k = 0; k < nDev; k++) warm.emplace_back(new Warm);
     std::atomic<int> ctxUp(0), parked(0); double tCtxUp = 0;
-    // read depth on the device: one array per index image, enabled by every context of the image (the first makes it); depthCtx[k] = 1 + a context of device k
-    // that feeds it.  Without the entry points (a build without them) or when the stage is refused, the formatters count everything.
-    const bool depthDevice = depth && deviceFilter && DepthTrack::deviceEntryPoints() && getenv("YAHA_HOST_DEPTH") == nullptr;
-    std::vector<std::atomic<int>> depthCtx(nDev); for (auto &x : depthCtx) x = 0;
-    // the evidence track on the device: the same arrangement (YAHA_HOST_EVENTS: the formatters count everything)
-    const bool eventsDevice = events && deviceFilter && EventsTrack::deviceEntryPoints() && getenv("YAHA_HOST_EVENTS") == nullptr;
-    std::vector<std::atomic<int>> eventsCtx(nDev); for (auto &x : eventsCtx) x = 0;
+    for (auto &T : tracks) T.onDevice = deviceFilter && T.track->deviceEntryPoints() && getenv(T.hostSwitch) == nullptr;
     // the junctions on the device: per context and per batch, nothing shared (YAHA_HOST_JUNCTIONS: the formatters make them all)
     const bool junctionsDevice = junctions && deviceFilter && JunctionTrack::deviceEntryPoints() && getenv("YAHA_HOST_JUNCTIONS") == nullptr;
     std::vector<std::atomic<uint64_t>> devReads(nDev); for (auto &x : devReads) x = 0;       // reads each device took (the stats line: do all devices pull their weight?)
@@ -387,21 +392,15 @@ int runQueries(Args &a, FILE *log)
         }
         { std::unique_lock<std::mutex> lk(W.mu); W.cv.wait(lk, [&] { return W.ready != 0; }); rc0 = W.ready == 1 ? 0 : (leadRc[d / perDev] ? leadRc[d / perDev] : YGPU_ENODEV); }
         if (rc0 == 0 && deviceFilter) rc0 = ygpu_set_postfilter(ctx[d], &PF);
-        bool ctxDepth = false;
-        if (rc0 == 0 && depthDevice) {
-            const int rcD = depth->deviceEnable(ctx[d]);
+        unsigned ctxOnDevice = 0;                                              // what the device stage does for this context's batches (Batch::onDevice)
+        for (size_t t = 0; t < tracks.size(); t++) if (rc0 == 0 && tracks[t].onDevice) {
+            const int rcT = tracks[t].track->deviceEnable(ctx[d]);
             // no room for the array beside the image and the arenas: the run stops here, before its first batch, with the sizes (a host array would hide that the
-            // device is full; a larger -covbin is the way out).  Any other refusal: this context's records are counted by the formatters.
-            if (rcD == YGPU_ENOMEM) { char m[640]; snprintf(m, sizeof m, "-ocov: %s", ygpu_last_error(ctx[d])); fail(m); }
-            else if (rcD == 0) { ctxDepth = true; int none = 0; depthCtx[d / perDev].compare_exchange_strong(none, d + 1); }
+            // device is full; larger bins are the way out).  Any other refusal: this context's records are counted by the formatters.
+            if (rcT == YGPU_ENOMEM) { char m[640]; snprintf(m, sizeof m, "%s: %s", tracks[t].track->names.fileOpt, ygpu_last_error(ctx[d])); fail(m); }
+            else if (rcT == 0) { ctxOnDevice |= 1u << t; int none = 0; tracks[t].feeder[d / perDev].compare_exchange_strong(none, d + 1); }
         }
-        bool ctxEvents = false;
-        if (rc0 == 0 && eventsDevice) {                                        // (the same rules: no room stops the run before its first batch)
-            const int rcE = events->deviceEnable(ctx[d]);
-            if (rcE == YGPU_ENOMEM) { char m[640]; snprintf(m, sizeof m, "-oev: %s", ygpu_last_error(ctx[d])); fail(m); }
-            else if (rcE == 0) { ctxEvents = true; int none = 0; eventsCtx[d / perDev].compare_exchange_strong(none, d + 1); }
-        }
-        const bool ctxJunctions = rc0 == 0 && junctionsDevice && junctions->deviceEnable(ctx[d]) == 0;      // (refused: the formatters make this context's)
+        if (rc0 == 0 && junctionsDevice && junctions->deviceEnable(ctx[d]) == 0) ctxOnDevice |= kJunctionsOnDevice;      // (refused: the formatters make this context's)
         if (rc0 != 0) { char m[512];
             snprintf(m, sizeof m, "ygpu_init(device %d) failed: %d %s", dev, rc0, ctx[d] ? ygpu_last_error(ctx[d]) : (d == leadCtx ? "" : "(the device's first context failed)"));
             fail(m); }
@@ -425,7 +424,7 @@ int runQueries(Args &a, FILE *log)
             uint64_t nc = 0, no = 0;
             int rc = ygpu_postfilter(ctx[d]); if (rc == 0) rc = ygpu_filtered_size(ctx[d], &nc, &no); if (rc != 0) return rc;
             // (the batch's junctions: few, and on their way while the clumps are sized)
-            if (fb->junctionsOnDevice) { rc = junctions->deviceCollect(ctx[d], fb->jnDev, fb->jnDevStats); if (rc != 0) return rc; }
+            if (fb->onDevice & kJunctionsOnDevice) { rc = junctions->deviceCollect(ctx[d], fb->jnDev, fb->jnDevStats); if (rc != 0) return rc; }
             if (!fb->clumpStart.ensure(4 * (fb->nReads + 1)) || !fb->clumps.ensure(sizeof(ygpu_out_clump) * nc) || !fb->ops.ensure(4 * no)) return YGPU_ENOMEM;
             ygpu_filtered_batch fr; rc = ygpu_collect_filtered(ctx[d], (uint32_t *)fb->clumpStart.p, (ygpu_out_clump *)fb->clumps.p, (uint32_t *)fb->ops.p, &fr);
             res.n_clumps = fr.n_clumps; res.n_ops = fr.n_ops; return rc;
@@ -496,8 +495,7 @@ int runQueries(Args &a, FILE *log)
                 // (the batch lives until it is printed: no wait for its bytes here)
                 int rc = ygpu_upload_nowait(ctx[d], &rb); const double h1 = now(); if (rc == 0) rc = ygpu_run(ctx[d]); if (rc != 0) return rc;
                 const double h2 = now();
-                uint64_t nc = 0, no = 0; b->filtered = deviceFilter; b->depthOnDevice = deviceFilter && ctxDepth; b->eventsOnDevice = deviceFilter && ctxEvents;
-                b->junctionsOnDevice = deviceFilter && ctxJunctions;
+                uint64_t nc = 0, no = 0; b->filtered = deviceFilter; b->onDevice = deviceFilter ? ctxOnDevice : 0u;
                 if (!first) { usUpload += (uint64_t)((h1 - h0) * 1e3); usRun += (uint64_t)((h2 - h1) * 1e3); nLater++; }
                 if (deviceFilter && overlapFilter && !first) {                 // the filter thread takes it from here; this thread goes on with the next batch
                     filterIdle();
@@ -544,17 +542,19 @@ int runQueries(Args &a, FILE *log)
     auto formatter = [&]() {
         yaha_session local; local.args = A; local.genome.bases = S->genome.bases; local.genome.nBaseBytes = S->genome.nBaseBytes; local.genome.seqs = S->genome.seqs;
             local.genome.maxROff = S->genome.maxROff;
-        local.depth = depth.get(); local.events = events.get(); local.junctions = junctions.get();
+        for (auto &T : tracks) local.tracks.push_back(T.track.get());
+        local.junctions = junctions.get();
         BatchP b;
         while (fmtQ.pop(b)) {
             const double t0 = now(); b->text.clear();
             b->jnHost.clear(); local.jnOut = &b->jnHost; local.jnReads = local.jnSkipped = 0;
-            if (!(b->nReads && b->filtered && b->junctionsOnDevice)) { b->jnDev.clear(); b->junctionsOnDevice = false; memset(b->jnDevStats, 0, sizeof b->jnDevStats); }
+            if (!(b->nReads && b->filtered && (b->onDevice & kJunctionsOnDevice))) { b->jnDev.clear(); b->onDevice &= ~kJunctionsOnDevice;
+                memset(b->jnDevStats, 0, sizeof b->jnDevStats); }
             if (!stop && b->nReads && b->filtered) {
                 ygpu_filtered_batch fr; memset(&fr, 0, sizeof fr);
                 fr.n_reads = (uint32_t)b->nReads; fr.clump_start = (const uint32_t *)b->clumpStart.p; fr.clumps = (const ygpu_out_clump *)b->clumps.p;
                     fr.ops = (const uint32_t *)b->ops.p; fr.n_clumps = b->nClumps; fr.n_ops = b->nOps;
-                local.reads.swap(b->reads); formatFiltered(&local, &fr, b->text, b->depthOnDevice, b->eventsOnDevice, b->junctionsOnDevice); local.reads.swap(b->reads);
+                local.reads.swap(b->reads); formatFiltered(&local, &fr, b->text, b->onDevice); local.reads.swap(b->reads);
             } else if (!stop && b->nReads) {
                 ygpu_result_batch res; memset(&res, 0, sizeof res);
                 res.n_reads = (uint32_t)b->nReads; res.clump_start = (const uint32_t *)b->clumpStart.p; res.clumps = (const ygpu_clump *)b->clumps.p;
@@ -600,25 +600,15 @@ int runQueries(Args &a, FILE *log)
         (unsigned long long)ticketsIssued.load()); rcAll = 1; }
     // The command line (csrc/main.cpp) leaves right after this function: it sets YAHA_FAST_EXIT and lets the process exit release the device memory and the
     // page-locked buffers in one go, instead of a hipFree per buffer (a second of waiting at the end of every run, measured).  Library users get the orderly path.
-    // the read-depth track: every image's array added to the host's, the bedGraph written after the last alignment
-    if (depth && !stop && rcAll == 0) {
-        std::string derr;
-        for (int k = 0; k < nDev; k++) if (const int c1 = depthCtx[k].load()) {
-            const int rcD = depth->deviceCollect(ctx[c1 - 1], derr);
-            if (rcD != 0) { fprintf(log, "-ocov: collecting the coverage array of device %d failed (%d): %s\n", devs[k], rcD, derr.c_str()); rcAll = 1; }
+    // the binned tracks, in the table's order: every image's array added to the host's, the file written after the last alignment
+    for (auto &T : tracks) if (!stop && rcAll == 0) {
+        std::string terr; const BinnedTrack::Names &nm = T.track->names;
+        for (int k = 0; k < nDev; k++) if (const int c1 = T.feeder[k].load()) {
+            const int rcT = T.track->deviceCollect(ctx[c1 - 1], terr);
+            if (rcT != 0) { fprintf(log, "%s: collecting the %s array of device %d failed (%d): %s\n", nm.fileOpt, nm.array, devs[k], rcT, terr.c_str()); rcAll = 1; }
         }
         if (fflush(out) != 0) rcAll = 1;
-        if (rcAll == 0 && !depth->write(A.covFileName.c_str(), S->genome, derr)) { fprintf(log, "%s\n", derr.c_str()); rcAll = 1; }
-    }
-    // the evidence track: the same, after the depth track
-    if (events && !stop && rcAll == 0) {
-        std::string eerr;
-        for (int k = 0; k < nDev; k++) if (const int c1 = eventsCtx[k].load()) {
-            const int rcE = events->deviceCollect(ctx[c1 - 1], eerr);
-            if (rcE != 0) { fprintf(log, "-oev: collecting the evidence array of device %d failed (%d): %s\n", devs[k], rcE, eerr.c_str()); rcAll = 1; }
-        }
-        if (fflush(out) != 0) rcAll = 1;
-        if (rcAll == 0 && !events->write(A.evFileName.c_str(), S->genome, eerr)) { fprintf(log, "%s\n", eerr.c_str()); rcAll = 1; }
+        if (rcAll == 0 && !T.track->write(T.file->c_str(), S->genome, terr)) { fprintf(log, "%s\n", terr.c_str()); rcAll = 1; }
     }
     // the breakpoint calls: the run's junctions clustered and written, after the tracks
     uint64_t nJunctions = 0;
@@ -640,11 +630,9 @@ int runQueries(Args &a, FILE *log)
         for (int k = 0; k < nDev; k++) { char t[32]; snprintf(t, sizeof t, "%s%llu", k ? ", " : "", (unsigned long long)devReads[k].load()); per += t; }
         per += "]";
         char dstat[768] = "";
-        if (depth) snprintf(dstat, sizeof dstat, ", \"depth_bins\": %llu, \"depth_device_records\": %llu, \"depth_host_records\": %llu, \"depth_covered_bases\": %llu",
-            (unsigned long long)depth->nBins, (unsigned long long)depth->devRecords, (unsigned long long)depth->hostRecords, (unsigned long long)depth->coveredBases());
-        if (events) { const size_t at = strlen(dstat);
-            snprintf(dstat + at, sizeof dstat - at, ", \"events_bins\": %llu, \"events_device_records\": %llu, \"events_host_records\": %llu, \"events_counted\": %llu",
-                (unsigned long long)events->nBins, (unsigned long long)events->devRecords, (unsigned long long)events->hostRecords, (unsigned long long)events->counted()); }
+        for (auto &T : tracks) { const size_t at = strlen(dstat); const BinnedTrack &t = *T.track;
+            snprintf(dstat + at, sizeof dstat - at, T.statsFmt, (unsigned long long)t.nBins, (unsigned long long)t.devRecords, (unsigned long long)t.hostRecords,
+                (unsigned long long)t.sum()); }
         if (junctions) { const size_t at = strlen(dstat);
             snprintf(dstat + at, sizeof dstat - at, ", \"bp_device_reads\": %llu, \"bp_host_reads\": %llu, \"bp_junctions\": %llu, \"bp_clusters\": %llu",
                 (unsigned long long)junctions->devReads, (unsigned long long)junctions->hostReads, (unsigned long long)nJunctions, (unsigned long long)junctions->nClusters); }
@@ -700,34 +688,30 @@ int yaha_session_postfilter_params(yaha_session *s, ygpu_postfilter_params *p)
     yoqc::Params P; oqcParamsFromArgs(s->args, P, s->pfThr);
     if (!s->args.OQC || P.bppN < 0 || P.minNonOverlap < 1) { s->err = "the device post-filter takes OQC runs with non-negative break point costs and -MNO of at least 1 only";
         return YGPU_EINVAL; }
-    s->pfSeqStart.clear(); s->pfSeqLen.clear(); for (auto &sq : s->genome.seqs) { s->pfSeqStart.push_back(sq.start); s->pfSeqLen.push_back(sq.length); }
     memset(p, 0, sizeof *p);
     p->minNonOverlap = P.minNonOverlap; p->BPCost = P.BPCost; p->maxBPLog = P.maxBPLog; p->FBS = P.FBS; p->FBS_PSLength = P.FBS_PSLength; p->FBS_PSScore = P.FBS_PSScore;
-    p->bppVmin = P.bppVmin; p->bppN = P.bppN; p->bppThr = s->pfThr.data(); p->n_seqs = (uint32_t)s->pfSeqStart.size(); p->seq_start = s->pfSeqStart.data();
-        p->seq_length = s->pfSeqLen.data();
+    p->bppVmin = P.bppVmin; p->bppN = P.bppN; p->bppThr = s->pfThr.data(); p->n_seqs = (uint32_t)s->seqStart.size(); p->seq_start = s->seqStart.data();
+        p->seq_length = s->seqLen.data();
     return 0;
 }
 int yaha_session_depth_params(yaha_session *s, ygpu_depth_params *p)
 {
     if (!s || !p) return YGPU_EINVAL;
-    s->pfSeqStart.clear(); s->pfSeqLen.clear(); for (auto &sq : s->genome.seqs) { s->pfSeqStart.push_back(sq.start); s->pfSeqLen.push_back(sq.length); }
-    p->bin = (uint32_t)s->args.covBin; p->min_mapq = (uint32_t)s->args.covMinQ; p->n_seqs = (uint32_t)s->pfSeqStart.size(); p->seq_start = s->pfSeqStart.data();
-    p->seq_length = s->pfSeqLen.data();
+    p->bin = (uint32_t)s->args.covBin; p->min_mapq = (uint32_t)s->args.covMinQ; p->n_seqs = (uint32_t)s->seqStart.size(); p->seq_start = s->seqStart.data();
+    p->seq_length = s->seqLen.data();
     return 0;
 }
 int yaha_session_events_params(yaha_session *s, ygpu_events_params *p)
 {
     if (!s || !p) return YGPU_EINVAL;
-    s->evSeqStart.clear(); s->evSeqLen.clear(); for (auto &sq : s->genome.seqs) { s->evSeqStart.push_back(sq.start); s->evSeqLen.push_back(sq.length); }
-    p->bin = (uint32_t)s->args.evBin; p->min_mapq = (uint32_t)s->args.evMinQ; p->min_clip = (uint32_t)s->args.evMinClip; p->n_seqs = (uint32_t)s->evSeqStart.size();
-        p->seq_start = s->evSeqStart.data(); p->seq_length = s->evSeqLen.data();
+    p->bin = (uint32_t)s->args.evBin; p->min_mapq = (uint32_t)s->args.evMinQ; p->min_clip = (uint32_t)s->args.evMinClip; p->n_seqs = (uint32_t)s->seqStart.size();
+        p->seq_start = s->seqStart.data(); p->seq_length = s->seqLen.data();
     return 0;
 }
 int yaha_session_junction_params(yaha_session *s, ygpu_junction_params *p)
 {
     if (!s || !p) return YGPU_EINVAL;
-    s->jnSeqStart.clear(); s->jnSeqLen.clear(); for (auto &sq : s->genome.seqs) { s->jnSeqStart.push_back(sq.start); s->jnSeqLen.push_back(sq.length); }
-    p->min_mapq = (uint32_t)s->args.bpMinQ; p->n_seqs = (uint32_t)s->jnSeqStart.size(); p->seq_start = s->jnSeqStart.data(); p->seq_length = s->jnSeqLen.data();
+    p->min_mapq = (uint32_t)s->args.bpMinQ; p->n_seqs = (uint32_t)s->seqStart.size(); p->seq_start = s->seqStart.data(); p->seq_length = s->seqLen.data();
     return 0;
 }
 int yaha_session_emit_filtered(yaha_session *s, const ygpu_filtered_batch *r, const char **text, size_t *len)

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <new>
 #include "../../../include/yaha_hip.h"
+#include "../depth_core.h"
 
 namespace yaha {
 
@@ -141,45 +142,55 @@ struct Text {
 };
 void printClump(const Args &a, const Genome &g, const Read &r, const OutClump &oc, int primaryCount, Text &out);
 
-// ---- read depth along the reference (-ocov; depth.cpp, ../depth_core.h) -----------------------------------------------------------------------------------
-// The host's coverage array, in the layout the device uses (one routine, depth_core.h): the formatter threads add the records the device did NOT count -- runs
-// whose post-filter stays on the host (-dpf N, -OQC N, YAHA_HOST_OQC=1), the reads the device stage hands back unfiltered, and everything when the library has
-// no device entry points for depth or refuses to enable them -- with relaxed atomics.  At the end of the run the device's arrays (one per index image) are added
-// and the bedGraph is written.  The ygpu_depth_* entry points are looked up weakly: host code links and runs without them (the CPU tier's test doubles).
-struct DepthTrack {
+// ---- the binned tracks: read depth (-ocov) and the evidence track (-oev) (depth.cpp, events.cpp; ../depth_core.h, ../events_core.h) -----------------------
+// The host's array of a track, in the layout the device uses (one routine a kind, *_core.h): `channels` uint32 a bin, bin-major.  The formatter threads add the
+// records the device did NOT count -- runs whose post-filter stays on the host (-dpf N, -OQC N, YAHA_HOST_OQC=1), the reads the device stage hands back
+// unfiltered, and everything when the library has no device entry points for the track or refuses to enable them -- with relaxed atomics.  At the end of the
+// run the device's arrays (one per index image) are added and the file is written after the last alignment.  A kind adds what differs: what a record adds, the
+// parameters of its device stage, its entry points -- looked up weakly: host code links and runs without them (the CPU tier's test doubles) -- and its lines.
+struct BinnedTrack {
+    // the words a kind is spoken of with: the options of the bin size and of the file, the array's noun, the file's
+    struct Names { const char *binOpt, *fileOpt, *array, *file; };
+    typedef int (*SizeFn)(ygpu_ctx *, uint64_t *);
+    typedef int (*CollectFn)(ygpu_ctx *, uint32_t *, uint64_t[4]);
+    // what the kind is: how it is spoken of, its words a bin, its device entry points (null in a build without them)
+    const Names names; const uint32_t channels;
+  private:
+    const bool haveEnable; const SizeFn devSize; const CollectFn devCollect;
+  public:
     std::vector<uint32_t> seqStart, seqLength, binBase; uint64_t nBins = 0; uint32_t bin = 100, minMapq = 0;
-    uint32_t *cov = nullptr;                                              // nBins words, zeroed; relaxed atomic adds
+    uint32_t *data = nullptr;                                             // nBins * channels words, zeroed; relaxed atomic adds
     uint64_t hostRecords = 0, hostSkipped = 0, hostDropped = 0;           // (atomic adds as well) records the host counted / gated by MAPQ / dropped
     uint64_t devRecords = 0, devSkipped = 0, devDropped = 0, devHandedBack = 0;
-    DepthTrack() {} DepthTrack(const DepthTrack &) = delete; DepthTrack &operator=(const DepthTrack &) = delete;
-    ~DepthTrack() { free(cov); }
+    BinnedTrack(const BinnedTrack &) = delete; BinnedTrack &operator=(const BinnedTrack &) = delete;
+    virtual ~BinnedTrack() { free(data); }
     bool init(const Genome &g, int binBases, int minQ, std::string &err);
-    void add(const OutClump &oc);                                         // one record printClump was called for
-    static bool deviceEntryPoints();                                      // does this build have ygpu_depth_*?
-    int  deviceEnable(ygpu_ctx *ctx) const;                               // YGPU_ENODEV without the entry points
+    virtual void add(const OutClump &oc, int qlen) = 0;                   // one record printClump was called for, and its read's length
+    bool deviceEntryPoints() const { return haveEnable && devSize && devCollect; }      // does this build have the kind's ygpu_*_enable / _size / _collect?
+    virtual int deviceEnable(ygpu_ctx *ctx) const = 0;                    // YGPU_ENODEV without the entry points
     int  deviceCollect(ygpu_ctx *ctx, std::string &err);                  // adds the image's array and statistics to this track
-    uint64_t coveredBases() const;
-    bool write(const char *path, const Genome &g, std::string &err) const;      // bedGraph; path "stdout" = standard output
-};
-
-// ---- the evidence track (-oev; events.cpp, ../events_core.h) ----------------------------------------------------------------------------------------------
-// The host's array of the track -- mismatched bases, deleted bases, insertions, clipped ends left and right: five uint32 a bin, bin-major, on the bins of the
-// depth track -- with DepthTrack's division of labour: the formatter threads add the records the device did NOT count (relaxed atomics), the device's arrays
-// (one per index image) are added at the end of the run and the file is written after the last alignment.  The ygpu_events_* entry points are looked up weakly.
-struct EventsTrack {
-    std::vector<uint32_t> seqStart, seqLength, binBase; uint64_t nBins = 0; uint32_t bin = 100, minMapq = 0, minClip = 1;
-    uint32_t *ev = nullptr;                                               // nBins * 5 words, zeroed; relaxed atomic adds
-    uint64_t hostRecords = 0, hostSkipped = 0, hostDropped = 0;           // (atomic adds as well) records the host counted / gated by MAPQ / dropped
-    uint64_t devRecords = 0, devSkipped = 0, devDropped = 0, devHandedBack = 0;
-    EventsTrack() {} EventsTrack(const EventsTrack &) = delete; EventsTrack &operator=(const EventsTrack &) = delete;
-    ~EventsTrack() { free(ev); }
-    bool init(const Genome &g, int binBases, int minQ, int minClipBases, std::string &err);
-    void add(const OutClump &oc, int qlen);                               // one record printClump was called for, and its read's length
-    static bool deviceEntryPoints();                                      // does this build have ygpu_events_*?
-    int  deviceEnable(ygpu_ctx *ctx) const;                               // YGPU_ENODEV without the entry points
-    int  deviceCollect(ygpu_ctx *ctx, std::string &err);                  // adds the image's array and statistics to this track
-    uint64_t counted() const;                                             // the sum over all bins and channels
+    uint64_t sum() const;                                                 // over all bins and channels
     bool write(const char *path, const Genome &g, std::string &err) const;      // path "stdout" = standard output
+  protected:
+    BinnedTrack(const Names &nm, uint32_t ch, bool enable, SizeFn sz, CollectFn co) : names(nm), channels(ch), haveEnable(enable), devSize(sz), devCollect(co) {}
+    ydepth::Layout layout() const { return ydepth::Layout{seqStart.data(), seqLength.data(), binBase.data(), (uint32_t)seqStart.size(), bin, minMapq}; }
+    void countRecord(int gate);                                           // what became of a record the host walked (ydepth::COUNTED ...)
+    virtual bool writeLines(FILE *f, const Genome &g) const = 0;          // the kind's lines; false: a write failed
+};
+struct DepthTrack : BinnedTrack {                                         // bedGraph of the covered bases
+    DepthTrack();
+    void add(const OutClump &oc, int qlen) override;
+    int  deviceEnable(ygpu_ctx *ctx) const override;
+  protected:
+    bool writeLines(FILE *f, const Genome &g) const override;
+};
+struct EventsTrack : BinnedTrack {                                        // mismatched bases, deleted bases, insertions, clipped ends left and right
+    uint32_t minClip = 1;
+    explicit EventsTrack(int minClipBases);
+    void add(const OutClump &oc, int qlen) override;
+    int  deviceEnable(ygpu_ctx *ctx) const override;
+  protected:
+    bool writeLines(FILE *f, const Genome &g) const override;
 };
 
 // ---- split-read breakpoint calls (-obp; junctions.cpp, ../junction_core.h) ---------------------------------------------------------------------------------
