@@ -267,6 +267,43 @@ def test_small_batch_then_large_batch_on_one_context(work, index11, monkeypatch)
         assert len(exp) > 100 and got == exp and redone == exp and again == exp
 
 
+def test_an_align_stage_that_overflows_its_arenas_is_redone(work, index11, monkeypatch, tmp_path):
+    """The align stage sizes its phase-1 arenas (state ops, gap ops) and its output arenas from the batch and redoes itself with twice as much when a kernel
+    reports one full (stage_align.hip: AlignOutcome).  YGPU_ALIGN_CAPS=s:o sets the first attempt's state-op capacity and its two output capacities (0: the
+    default), so that a small batch overflows them: both redos, and a run without the switch behind them, give the records of a fresh context.  That the
+    stage really repeated shows in the library's YGPU_STATS lines; that switch is read once per process, so those come from the command line in a child process.
+    Attempts a fresh context needs on this batch (132 reads), observed: 13, 11, 9, 7, 5 for s = 16, 64, 256, 1024, 4096 and 13, 11, 9, 7, 5 for o = 4, 16, 64, 256,
+    1024 -- the values below give 5 and 5."""
+    reads = os.path.join(work, "r1k.fa")
+    with ya.Session(["-x", index11, "-q", reads]) as s:
+        large = s.next_batch(600)
+        with ya.Context(s.index, s.params) as fresh:
+            fresh.upload(large); fresh.run(); exp = ya.result_records(fresh.collect())
+        assert len(exp) > 100
+        with ya.Context(s.index, s.params) as ctx:
+            for caps in (CAPS_STATE, CAPS_OUT):
+                monkeypatch.setenv("YGPU_ALIGN_CAPS", caps)
+                ctx.upload(large); ctx.run()
+                assert ya.result_records(ctx.collect()) == exp, "redone with YGPU_ALIGN_CAPS=" + caps
+            monkeypatch.delenv("YGPU_ALIGN_CAPS")
+            ctx.upload(large); ctx.run()
+            assert ya.result_records(ctx.collect()) == exp
+    import re
+    out = str(tmp_path / "o.sam"); ref = golden_lines("r1k_default")
+    for caps, why in ((CAPS_STATE, "repeated (phase-1 arenas"), (CAPS_OUT, "repeated (output arenas)")):
+        p = subprocess.run([ya.CLI_PATH, "-x", index11, "-q", reads, "-osh", out, "-ctx", "1"], stderr=subprocess.PIPE, env=dict(os.environ, YGPU_STATS="1", YGPU_ALIGN_CAPS=caps))
+        err = p.stderr.decode()
+        assert p.returncode == 0, err[-1500:]
+        attempts = [int(a) for a in re.findall(r"align attempts (\d+)", err)]
+        print("YGPU_ALIGN_CAPS=%s: align attempts %r" % (caps, attempts))
+        assert why in err and attempts and all(2 <= a <= 12 for a in attempts), err[-1500:]
+        assert strip_pg(open(out).read()) == ref
+
+
+# (the capacities double from one attempt to the next and the stage gives up after 24)
+CAPS_STATE, CAPS_OUT = "4096:0", "0:1024"
+
+
 def test_cli_drop_in(work, index11, tmp_path):
     out = str(tmp_path / "o.sam")
     subprocess.check_call([ya.CLI_PATH, "-x", index11, "-q", os.path.join(work, "rchim.fa"), "-osh", out, "-FBS", "Y", "-t", "4", "-batch", "64"], stderr=subprocess.DEVNULL)

@@ -210,8 +210,7 @@ struct ygpu_ctx {
     bool jnSet = false, jnDone = false, jnHaveTotal = false;       // enabled; the last ygpu_postfilter made them; their number has been fetched
     uint32_t jnMinMapq = 0, jnNSeqs = 0, jnReads = 0, jnTotal = 0; // jnReads: reads of the batch they belong to (0: an empty batch, nothing on the device)
     // stage state
-    uint32_t hOutCounts[2] = {0, 0}, hOutEf = 0;
-    bool hOutValid = false;
+    uint32_t hOutCounts[2] = {0, 0};      // output clumps and ops of the align stage, fetched with its last wait
     uint32_t nHits = 0, nFrags = 0, nRegions = 0, nMulti = 0, nTiny = 0, nSmall = 0, nMid = 0, nBig = 0, maxN = 0;
     int sortRankUsed = 0;                // the ranking the batch's hits were sorted with (stage_seed.hip: 0 = LDS atomics, 1 = ballots)
     bool sortRankForced = false;         // ... because YGPU_SORT_RANK said so
