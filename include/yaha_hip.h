@@ -256,6 +256,47 @@ int  ygpu_events_size(ygpu_ctx *ctx, uint64_t *n_bins);
  * contexts' included.  stats (may be NULL): records counted, records skipped (MAPQ), records dropped (two sequences), reads left to the caller. */
 int  ygpu_events_collect(ygpu_ctx *ctx, uint32_t *counts, uint64_t stats[4]);
 
+/* ---- the allele pileup: which base the printed alignments carry at every reference base (optional, behind ygpu_postfilter) ------------------------------------
+ * The allele-resolved member of the family: the tracks above say that a bin holds mismatches, this one says which base the reads carry there and how many of
+ * them agree.  With ygpu_pileup_enable, every ygpu_postfilter of the context also adds the clumps it returns to pu[slot][channel] (uint32, slot-major, seven
+ * channels A C G T N DEL INS) on the bin layout of the depth track with a bin of ONE base: a slot per reference base, sequence by sequence.  The contract
+ * (yaha_amd/csrc/pileup_core.h -- one set of routines for host and device): every reference base under an M or R op adds 1 to the channel of the read's base
+ * there (the reverse-complement base for a reversed clump, i.e. what SEQ shows: reference orientation; codes other than A C G T: N), every reference base under a
+ * D op adds 1 to DEL, every I op adds 1 to INS at the next reference base the walk reaches (kept inside the record); a base whose query offset lies past the
+ * clump's eqo adds nothing, whatever the ops add up to.  Base qualities are not used.  As for depth: a clump that spans two sequences is not printed and adds
+ * nothing, records with mapQuality < min_mapq add nothing, a count that passes 2^32 - 1 wraps, and reads that come back UNFILTERED (primaryCount == 0xFFFF) are
+ * NOT counted: the caller filters them and counts what it prints.  While the pileup is enabled ygpu_postfilter_snapshot also copies the batch's forward codes
+ * and read offsets (device to device, into buffers of the snapshot's own): the stage reads the bases when the context may already hold its next batch.
+ * ONE array per index image, 28 * n_slots bytes of device memory (a 3.1 Gbp genome is 86.8 GB), shared by the image's contexts once each of them has called
+ * ygpu_pileup_enable with the same parameters -- the first call makes and zeroes it, the others join; other parameters are refused.  When it does not fit:
+ * YGPU_ENOMEM, the sizes in ygpu_last_error.  It lives until the last of those contexts is destroyed; ygpu_park does not touch it.
+ * An array of that size does not travel: a SITE is a slot with nonref = A + C + G + T + N + DEL - pu[slot][channel of the reference's own base] + INS >= some
+ * threshold >= 1, and the device selects the CANDIDATES -- the slots with nonref >= 1, ascending -- itself (ygpu_pileup_candidates_size runs the selection over
+ * the array as it stands, ygpu_pileup_candidates_collect copies the slot numbers); ygpu_pileup_gather returns the seven counts of every slot of a caller's
+ * list.  With several images: candidates of each, the sorted union, a gather on each, the sums, the threshold -- nothing is lost, since a slot whose summed
+ * nonref is at least 1 has nonref >= 1 in some image.  These three calls wait for everything queued on the device and use the post-filter's side of the
+ * context: call them between batches or at the end of the run, not while a ygpu_postfilter of the context is running.  They, and ygpu_pileup_collect, also
+ * work on a context that has been parked (ygpu_park): the array is the image's, and the few work buffers they need are made again.
+ * This is the first track whose kernel reads the SNAPSHOT after the stage's last wait of the host (the forward codes, for the bases): ygpu_postfilter returns
+ * with that kernel still queued, so the rule of ygpu_postfilter_snapshot holds in earnest here -- the next snapshot of the context may be taken only once the
+ * filtered results of this one have been collected (ygpu_collect_filtered waits behind the kernel), not as soon as ygpu_postfilter has returned.
+ * Order: ygpu_set_postfilter, ygpu_pileup_enable, then batches (ygpu_run, ygpu_postfilter ...), then the candidates and gathers (or ygpu_pileup_collect). */
+#define YGPU_PILEUP_CHANNELS 7
+typedef struct ygpu_pileup_params {
+    uint32_t min_mapq, n_seqs;
+    const uint32_t *seq_start, *seq_length;            /* reference sequences in bases, ascending (host memory; copied) */
+} ygpu_pileup_params;
+int  ygpu_pileup_enable(ygpu_ctx *ctx, const ygpu_pileup_params *p);           /* after ygpu_set_postfilter */
+int  ygpu_pileup_size(ygpu_ctx *ctx, uint64_t *n_slots);
+/* The image's whole array as it stands, into counts[n_slots * 7], slot-major (may be NULL) -- for tests and small genomes: waits for every filter stage queued so
+ * far on the device.  stats (may be NULL): records counted, records skipped (MAPQ), records dropped (two sequences), reads left to the caller, counts added
+ * (the sum over the array while nothing has wrapped). */
+int  ygpu_pileup_collect(ygpu_ctx *ctx, uint32_t *counts, uint64_t stats[5]);
+int  ygpu_pileup_candidates_size(ygpu_ctx *ctx, uint64_t *n);                  /* selects; *n = candidates of the array as it stands */
+int  ygpu_pileup_candidates_collect(ygpu_ctx *ctx, uint32_t *slots);           /* slots[n] of the last ygpu_pileup_candidates_size, ascending */
+/* rows[n * 7]: the seven counts of slots[0 .. n) (host memory; ascending for locality, not checked; a slot past the array reads as zeros). */
+int  ygpu_pileup_gather(ygpu_ctx *ctx, const uint32_t *slots, uint64_t n, uint32_t *rows);
+
 /* ---- split-read breakpoint calls: where the printed alignments of a read join (optional, behind ygpu_postfilter) ----------------------------------------------
  * The primary signal of a structural-variant caller.  With ygpu_junctions_enable, every ygpu_postfilter of the context also makes the JUNCTIONS of its batch on
  * the device.  The contract (yaha_amd/csrc/junction_core.h -- one set of routines for host and device): the eligible records of a read are the printed ones (a
@@ -395,6 +436,8 @@ int  yaha_session_emit_filtered(yaha_session *s, const ygpu_filtered_batch *r, c
 int  yaha_session_depth_params(yaha_session *s, ygpu_depth_params *p);
 /* The same for ygpu_events_enable: -evbin (default 100), -evq (default 0), -evclip (default 1) and the sequence table (pointers of their own into the session). */
 int  yaha_session_events_params(yaha_session *s, ygpu_events_params *p);
+/* The same for ygpu_pileup_enable: -puq (default 0) and the sequence table (pointers of their own into the session). */
+int  yaha_session_pileup_params(yaha_session *s, ygpu_pileup_params *p);
 /* The same for ygpu_junctions_enable: -bpq (default 0) and the sequence table (pointers of their own into the session). */
 int  yaha_session_junction_params(yaha_session *s, ygpu_junction_params *p);
 /* `yaha -g genome.fa [-L k] [-S s] [-H h]`: writes genome.nib2 and genome.X<LL>_<SS>_<HHHHH>S (Main.c:554-628). */

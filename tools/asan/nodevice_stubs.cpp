@@ -35,6 +35,12 @@ int  ygpu_depth_collect(ygpu_ctx *, uint32_t *, uint64_t *) { return YGPU_ENODEV
 int  ygpu_events_enable(ygpu_ctx *, const ygpu_events_params *) { return YGPU_ENODEV; }
 int  ygpu_events_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
 int  ygpu_events_collect(ygpu_ctx *, uint32_t *, uint64_t *) { return YGPU_ENODEV; }
+int  ygpu_pileup_enable(ygpu_ctx *, const ygpu_pileup_params *) { return YGPU_ENODEV; }
+int  ygpu_pileup_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
+int  ygpu_pileup_collect(ygpu_ctx *, uint32_t *, uint64_t *) { return YGPU_ENODEV; }
+int  ygpu_pileup_candidates_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
+int  ygpu_pileup_candidates_collect(ygpu_ctx *, uint32_t *) { return YGPU_ENODEV; }
+int  ygpu_pileup_gather(ygpu_ctx *, const uint32_t *, uint64_t, uint32_t *) { return YGPU_ENODEV; }
 int  ygpu_junctions_enable(ygpu_ctx *, const ygpu_junction_params *) { return YGPU_ENODEV; }
 int  ygpu_junctions_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
 int  ygpu_junctions_collect(ygpu_ctx *, ygpu_junction *, uint64_t *) { return YGPU_ENODEV; }

@@ -86,6 +86,14 @@ class EventsParams(C.Structure):
 EVENTS_CHANNELS = ("mismatch", "deleted", "insertion", "clip_left", "clip_right")
 
 
+class PileupParams(C.Structure):
+    _fields_ = [("min_mapq", C.c_uint32), ("n_seqs", C.c_uint32), ("seq_start", C.c_void_p), ("seq_length", C.c_void_p)]
+
+
+PILEUP_CHANNELS = ("A", "C", "G", "T", "N", "del", "ins")
+PILEUP_STATS = DEPTH_STATS + ("counts_added",)
+
+
 class JunctionParams(C.Structure):
     _fields_ = [("min_mapq", C.c_uint32), ("n_seqs", C.c_uint32), ("seq_start", C.c_void_p), ("seq_length", C.c_void_p)]
 
@@ -119,6 +127,8 @@ EXPORTS = (
     "ygpu_device_count", "ygpu_init", "ygpu_init_multi", "ygpu_clone", "ygpu_destroy", "ygpu_last_error", "ygpu_memory", "ygpu_park", "ygpu_get_arena_profile", "ygpu_presize", "ygpu_upload", "ygpu_upload_nowait", "ygpu_run", "ygpu_collect", "ygpu_result_size", "ygpu_collect_into", "ygpu_host_alloc", "ygpu_host_free", "ygpu_set_postfilter", "ygpu_postfilter_snapshot", "ygpu_postfilter", "ygpu_postfilter_drop", "ygpu_inject_results", "ygpu_selftest_primitives", "ygpu_trace_volume", "ygpu_filtered_size", "ygpu_collect_filtered", "ygpu_last_timing",
     "ygpu_depth_enable", "ygpu_depth_size", "ygpu_depth_collect", "yaha_session_depth_params",
     "ygpu_events_enable", "ygpu_events_size", "ygpu_events_collect", "yaha_session_events_params",
+    "ygpu_pileup_enable", "ygpu_pileup_size", "ygpu_pileup_collect", "ygpu_pileup_candidates_size", "ygpu_pileup_candidates_collect", "ygpu_pileup_gather",
+    "yaha_session_pileup_params",
     "ygpu_junctions_enable", "ygpu_junctions_size", "ygpu_junctions_collect", "yaha_session_junction_params",
     "ygpu_submit", "ygpu_poll", "ygpu_wait", "ygpu_seed_join", "ygpu_chain", "ygpu_dp_batch", "ygpu_dp_batch_ex",
     "yaha_session_open", "yaha_session_close", "yaha_session_error", "yaha_session_params",
@@ -302,7 +312,7 @@ class Context:
         fills); returns (object, n, the statistics as a dict)."""
         n = C.c_uint64()
         self._check(size(self._h, C.byref(n)), size.__name__)
-        out, arg = make(n.value); st = (C.c_uint64 * 4)()
+        out, arg = make(n.value); st = (C.c_uint64 * max(4, len(stat_names)))()
         self._check(collect(self._h, arg, st), collect.__name__)
         return out, n.value, {k: int(st[i]) for i, k in enumerate(stat_names)}
 
@@ -331,6 +341,34 @@ class Context:
         """(evidence array of the context's index image as it stands -- numpy uint32 of shape (n_bins, 5), channels EVENTS_CHANNELS -- and the statistics as a dict)."""
         ev, n, st = self._collect(lib().ygpu_events_size, lib().ygpu_events_collect, lambda n: self._bins((max(1, n), len(EVENTS_CHANNELS))), DEPTH_STATS)
         return ev[:n], st
+
+    def pileup_enable(self, session):
+        """The allele pileup of the printed clumps behind postfilter() (ygpu_pileup_enable), with the session's -puq and sequence table.  After
+        set_postfilter(); the contexts of one index image share one array, 28 bytes a reference base."""
+        self._enable(lib().yaha_session_pileup_params, lib().ygpu_pileup_enable, PileupParams(), session)
+
+    def pileup_collect(self):
+        """(the whole pileup array of the context's index image as it stands -- numpy uint32 of shape (n_slots, 7), channels PILEUP_CHANNELS -- and the
+        statistics as a dict).  For tests and small genomes: pileup_candidates() and pileup_gather() are the way at scale."""
+        pu, n, st = self._collect(lib().ygpu_pileup_size, lib().ygpu_pileup_collect, lambda n: self._bins((max(1, n), len(PILEUP_CHANNELS))), PILEUP_STATS)
+        return pu[:n], st
+
+    def pileup_candidates(self):
+        """The slots of the image's array where at least one read disagrees with the reference, ascending (numpy uint32), selected on the device."""
+        import numpy as np
+        n = C.c_uint64()
+        self._check(lib().ygpu_pileup_candidates_size(self._h, C.byref(n)), "ygpu_pileup_candidates_size")
+        out = np.zeros(max(1, n.value), dtype=np.uint32)
+        self._check(lib().ygpu_pileup_candidates_collect(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))), "ygpu_pileup_candidates_collect")
+        return out[:n.value]
+
+    def pileup_gather(self, slots):
+        """The seven counts of every slot of `slots` (ascending; any integer sequence): numpy uint32 of shape (len(slots), 7)."""
+        import numpy as np
+        sl = np.ascontiguousarray(slots, dtype=np.uint32); rows = np.zeros((max(1, len(sl)), len(PILEUP_CHANNELS)), dtype=np.uint32)
+        self._check(lib().ygpu_pileup_gather(self._h, sl.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_uint64(len(sl)), rows.ctypes.data_as(C.POINTER(C.c_uint32))),
+                    "ygpu_pileup_gather")
+        return rows[:len(sl)]
 
     def junctions_enable(self, session):
         """Split-read junctions of every batch behind postfilter() (ygpu_junctions_enable), with the session's -bpq and sequence table.  After set_postfilter()."""

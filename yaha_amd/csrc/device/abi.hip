@@ -362,7 +362,8 @@ std::vector<DevBuf *> allBuffers(ygpu_ctx *ctx)
                          &ctx->oqCs, &ctx->oqCl, &ctx->oqOpsIn, &ctx->oqSeeds, &ctx->oqQlen, &ctx->pf.scanState, &ctx->pf.counters, &ctx->oqProf, &ctx->oqLists, &ctx->oqClsCnt,
                              &ctx->oqThr, &ctx->oqSeqStart, &ctx->oqSeqLen, &ctx->oqNeed, &ctx->oqPoolOff, &ctx->oqKeys, &ctx->oqStack, &ctx->oqNodes, &ctx->oqPrim, &ctx->oqPA,
                              &ctx->oqPfx, &ctx->oqPath, &ctx->oqPool, &ctx->oqPush, &ctx->oqOut, &ctx->oqOutCnt, &ctx->oqOutOps, &ctx->oqPrimCnt, &ctx->oqOutStart,
-                             &ctx->oqOpsStart, &ctx->oqFClumps, &ctx->oqFOps, &ctx->jnCnt, &ctx->jnStart, &ctx->jnOut, &ctx->jnStats, &ctx->jnSeqStart, &ctx->jnSeqLen};
+                             &ctx->oqOpsStart, &ctx->oqFClumps, &ctx->oqFOps, &ctx->jnCnt, &ctx->jnStart, &ctx->jnOut, &ctx->jnStats, &ctx->jnSeqStart, &ctx->jnSeqLen,
+                         &ctx->puFwd, &ctx->puReadOff, &ctx->puTileCnt, &ctx->puTileStart, &ctx->puCand, &ctx->puSlots, &ctx->puRows};
     return std::vector<DevBuf *>(all, all + sizeof all / sizeof all[0]);
 }
 extern "C" {

@@ -119,8 +119,9 @@ struct PfSide {
 // ../events_core.h: yevents::NCH uint32 channels a bin) -- keep ONE array per kind and index image, which the contexts that share the image (ygpu_clone,
 // ctx_per_device of ygpu_init_multi) feed together with global atomics.  Made by the image's first ygpu_depth_enable / ygpu_events_enable, held by every
 // context that enabled it, released with the last of them (never by ygpu_park: a parked sibling keeps its reference and gives up nothing of the image's).
-// The two arrays of an image are independent: each has its own bins, gates and sequence table.
-enum { TRACK_DEPTH = 0, TRACK_EVENTS = 1, TRACK_KINDS };
+// The allele pileup (-opu; pileup_stage.h, ../pileup_core.h: ypileup::NCH channels a reference base, the bin fixed at 1) is the third kind.
+// The arrays of an image are independent: each has its own bins, gates and sequence table.
+enum { TRACK_DEPTH = 0, TRACK_EVENTS = 1, TRACK_PILEUP = 2, TRACK_KINDS };
 struct TrackImage {
     int device = 0;
     DevBuf data, stats, seqStart, seqLength, binBase;
@@ -203,7 +204,13 @@ struct ygpu_ctx {
     DevCounters snapCtrPlain{};
     unsigned long long snapHits = 0, snapFrags = 0, snapRegions = 0;
     DevBuf oqCs, oqCl, oqOpsIn, oqSeeds, oqQlen;
-    std::shared_ptr<TrackImage> track[TRACK_KINDS];      // set by ygpu_depth_enable / ygpu_events_enable: the post-filter then feeds the image's array of that kind
+    // set by ygpu_depth_enable / ygpu_events_enable / ygpu_pileup_enable: the post-filter then feeds the image's array of that kind
+    std::shared_ptr<TrackImage> track[TRACK_KINDS];
+    // the allele pileup (pileup_stage.h): the snapshot's own copy of the batch's forward codes and read offsets (taken only while the pileup is enabled -- the
+    // kernel reads the bases when the context may already be uploading its next batch); the end of the run: candidates per tile and their exclusive sums, the
+    // candidate slots, a caller's slot list and the rows gathered for it
+    DevBuf puFwd, puReadOff, puTileCnt, puTileStart, puCand, puSlots, puRows;
+    uint64_t puNCand = 0; bool puHaveCand = false;
     // split-read junctions (-obp; junction_stage.h, ../junction_core.h): made per batch behind the post-filter, in buffers of the context's own -- counts and
     // their exclusive sums per read, the junctions (sized from the batch's filtered clump count), four statistics words, a sequence table of their own
     DevBuf jnCnt, jnStart, jnOut, jnStats, jnSeqStart, jnSeqLen;

@@ -1,11 +1,13 @@
 // stage_out.hip -- what leaves the device: the batch's results as ygpu_run left them (ygpu_collect*), and the post-filter stage (postFilterBySimilarity,
 // GraphPath.cpp:897-1086, Query.c:450) on a snapshot of them -- oqc_stage.h -- with its own stream, wait slot and look-back words (PfSide); behind it, when
 // ygpu_depth_enable asked for it, the read-depth track of the printed clumps (depth_stage.h), and when ygpu_events_enable did, their evidence track
-// (events_stage.h); and when ygpu_junctions_enable did, the batch's split-read junctions (junction_stage.h), which leave with the filtered batch.
+// (events_stage.h), and when ygpu_pileup_enable did, their allele pileup (pileup_stage.h: the one track that reads the reads' bases, which the snapshot then copies
+// as well); and when ygpu_junctions_enable did, the batch's split-read junctions (junction_stage.h), which leave with the filtered batch.
 #include "ctx.h"
 #include "oqc_stage.h"
 #include "depth_stage.h"
 #include "events_stage.h"
+#include "pileup_stage.h"
 #include "junction_stage.h"
 #include <map>
 #include <tuple>
@@ -81,6 +83,13 @@ int ygpu_postfilter_snapshot(ygpu_ctx *ctx)
     if (O) HIPCHK(hipMemcpyAsync(ctx->oqOpsIn.p, ctx->outOps.p, 4ull * O, hipMemcpyDeviceToDevice, ctx->stream));
     if (n) KL(k_oqc_seeds, dim3(gridFor(n, 256)), dim3(256), 0, ctx->stream, ctx->dFwd.as<uint8_t>(), ctx->dReadOff.as<uint32_t>(), n, ctx->oqSeeds.as<uint32_t>(),
         ctx->oqQlen.as<uint32_t>());
+    // the allele pileup reads the reads' bases behind the filter, when the next upload may have overwritten them: the forward codes (the reverse strand's channel
+    // follows from them, pileup_core.h) and the reads' offsets join the snapshot -- only on a context that enabled the pileup
+    if (ctx->track[TRACK_PILEUP] && n) {
+        ENSURE(ctx->puFwd, ctx->totalBases + 1); ENSURE(ctx->puReadOff, 4ull * (n + 1));
+        if (ctx->totalBases) HIPCHK(hipMemcpyAsync(ctx->puFwd.p, ctx->dFwd.p, ctx->totalBases, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->puReadOff.p, ctx->dReadOff.p, 4ull * (n + 1), hipMemcpyDeviceToDevice, ctx->stream));
+    }
     // (no wait here: the context's thread goes straight on to its next batch -- whatever it queues on this stream follows the copies -- and the work counters land
     // in a pinned slot the filter's side reads after its own first wait; without the slot, a wait it is)
     if (ctx->snapCtr) HIPCHK(hipMemcpyAsync(ctx->snapCtr, ctx->ctr.p, sizeof(DevCounters), hipMemcpyDeviceToHost, ctx->stream));
@@ -108,7 +117,8 @@ static ydepth::Layout trackLayout(const TrackImage &T)
 }
 // The binned tracks of the nClumps clumps just gathered -- the ones that get printed -- on the post-filter's stream, a wave a clump: the evidence track (the wave
 // finds its clump's read -- the query length of the right clip -- in oqOutStart; YGPU_EVENTS_DIRECT: every op's atomics without the combining in the wave, for
-// measurements; read at every call), then read depth and its count of the reads handed back.
+// measurements; read at every call), then read depth and its count of the reads handed back, then the allele pileup (the wave finds its clump's read the same
+// way, and the read's bases in the snapshot's copy of the forward codes).
 static int launchTracks(ygpu_ctx *full, uint32_t n, uint32_t nClumps)
 {
     PfSide *ctx = &full->pf;
@@ -126,6 +136,11 @@ static int launchTracks(ygpu_ctx *full, uint32_t n, uint32_t nClumps)
         DepthArgs D; D.L = trackLayout(*T); D.cov = T->data.as<uint32_t>(); D.nBins = (uint32_t)T->nBins; D.stats = T->stats.as<unsigned long long>();
         KL(k_depth_clumps, grid, block, 0, ctx->stream, D, fClumps, fOps, nClumps);
         KL(k_depth_handed_back, dim3(gridFor(n, 256)), block, 0, ctx->stream, full->oqOutCnt.as<uint32_t>(), full->oqPrimCnt.as<uint32_t>(), n, D.stats);
+    }
+    if (const TrackImage *T = full->track[TRACK_PILEUP].get()) {
+        PileupArgs P; P.L = trackLayout(*T); P.pu = T->data.as<uint32_t>(); P.nSlots = (uint32_t)T->nBins; P.stats = T->stats.as<unsigned long long>();
+        P.fwd = full->puFwd.as<uint8_t>(); P.readOff = full->puReadOff.as<uint32_t>();
+        KL(k_pileup_clumps, grid, block, 0, ctx->stream, P, fClumps, fOps, full->oqOutStart.as<uint32_t>(), n, nClumps);
     }
     return 0;
 }
@@ -230,7 +245,7 @@ static int postfilterBody(ygpu_ctx *full)
         KL(k_junction_emit, grid, dim3(256), 0, ctx->stream, J);
         full->jnReads = n; full->jnDone = true;
     }
-    // the binned tracks that are enabled (-oev, -ocov), behind the junctions on this stage's stream
+    // the binned tracks that are enabled (-oev, -ocov, -opu), behind the junctions on this stage's stream
     rc = launchTracks(full, n, tot[0]); if (rc) return rc;
     if (oqProf) {
         unsigned long long h[32 * YQ_NCLASS]; HIPCHK(hipMemcpyAsync(h, full->oqProf.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
@@ -246,13 +261,16 @@ static int postfilterBody(ygpu_ctx *full)
     full->oqDone = true;
     return 0;
 }
-// ---- the binned tracks: read depth and the evidence track (depth_stage.h, events_stage.h; the contracts are in ../depth_core.h and ../events_core.h) ---------
-// What tells the two kinds apart outside their kernels: the entry points' names and the array's noun for messages, the option that makes the array smaller,
-// the words a bin takes, and whether a clip length belongs to the parameters.
-struct TrackKind { int kind; const char *enable, *size, *collect, *noun, *counted, *binOpt; uint32_t channels; bool hasClip; };
-static const TrackKind kDepthKind = {TRACK_DEPTH, "ygpu_depth_enable", "ygpu_depth_size", "ygpu_depth_collect", "coverage", "depth is", "-covbin", 1, false};
+// ---- the binned tracks: read depth, the evidence track and the allele pileup (depth_stage.h, events_stage.h, pileup_stage.h; the contracts are in
+// ../depth_core.h, ../events_core.h and ../pileup_core.h) -----------------------------------------------------------------------------------------------------
+// What tells the kinds apart outside their kernels: the entry points' names and the array's noun for messages, the option that makes the array smaller (none:
+// the bin is fixed), the words a bin takes, whether a clip length belongs to the parameters, and the statistics words the stage keeps.
+struct TrackKind { int kind; const char *enable, *size, *collect, *noun, *counted, *binOpt; uint32_t channels; bool hasClip; uint32_t nStats; };
+static const TrackKind kDepthKind = {TRACK_DEPTH, "ygpu_depth_enable", "ygpu_depth_size", "ygpu_depth_collect", "coverage", "depth is", "-covbin", 1, false, 4};
 static const TrackKind kEventsKind = {TRACK_EVENTS, "ygpu_events_enable", "ygpu_events_size", "ygpu_events_collect", "evidence", "the events are", "-evbin",
-    (uint32_t)yevents::NCH, true};
+    (uint32_t)yevents::NCH, true, 4};
+static const TrackKind kPileupKind = {TRACK_PILEUP, "ygpu_pileup_enable", "ygpu_pileup_size", "ygpu_pileup_collect", "pileup", "the pileup is", nullptr,
+    (uint32_t)ypileup::NCH, false, 5};
 // the arrays of this process, by kind and by the image they belong to (the address of its bases on the device: what the contexts of an image share)
 static std::mutex gTrackMu;
 static std::map<std::tuple<int, int, const void *>, std::weak_ptr<TrackImage>> gTrackImages;
@@ -281,8 +299,9 @@ static int trackEnable(ygpu_ctx *ctx, const TrackKind &K, uint32_t bin, uint32_t
     if (T->data.ensureExact(bytes)) {                                       // (exact: a growth margin on 12 GB is 3 GB)
         (void)hipGetLastError(); size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) != hipSuccess) { fb = 0; (void)hipGetLastError(); }
         char perBin[32] = ""; if (K.channels > 1) snprintf(perBin, sizeof perBin, " (%u bytes a bin)", 4u * K.channels);
-        char m[256]; snprintf(m, sizeof m, "%sno room on device %d for the %s array: %.2f GB for %llu bins of %u bases%s, %.2f GB free (a larger %s needs less)", who.c_str(),
-            ctx->device, K.noun, bytes / 1e9, (unsigned long long)T->nBins, bin, perBin, fb / 1e9, K.binOpt);
+        const std::string wayOut = K.binOpt ? std::string("a larger ") + K.binOpt + " needs less" : std::string("the bin is fixed: a smaller -ctx leaves more");
+        char m[320]; snprintf(m, sizeof m, "%sno room on device %d for the %s array: %.2f GB for %llu bins of %u bases%s, %.2f GB free (%s)", who.c_str(),
+            ctx->device, K.noun, bytes / 1e9, (unsigned long long)T->nBins, bin, perBin, fb / 1e9, wayOut.c_str());
         ctx->err = m; return YGPU_ENOMEM;
     }
     if (T->stats.ensure(64) || T->seqStart.ensure(4ull * nSeqs) || T->seqLength.ensure(4ull * nSeqs) || T->binBase.ensure(4ull * (nSeqs + 1))) {
@@ -302,7 +321,7 @@ static int trackSize(ygpu_ctx *ctx, const TrackKind &K, uint64_t *n_bins)
     *n_bins = ctx->track[K.kind]->nBins; return 0;
 }
 // The image's array as it stands: every filter stage queued on the device so far -- this context's and its siblings' -- has finished when the copy is taken.
-static int trackCollect(ygpu_ctx *ctx, const TrackKind &K, uint32_t *words, uint64_t stats[4])
+static int trackCollect(ygpu_ctx *ctx, const TrackKind &K, uint32_t *words, uint64_t *stats /* K.nStats words */)
 {
     if (!ctx || !ctx->stream) return YGPU_EINVAL;
     if (!ctx->track[K.kind]) { ctx->err = std::string(K.collect) + ": " + K.enable + " has not been called on this context"; return YGPU_EINVAL; }
@@ -310,7 +329,7 @@ static int trackCollect(ygpu_ctx *ctx, const TrackKind &K, uint32_t *words, uint
     HIPCHK(hipDeviceSynchronize());
     const TrackImage &T = *ctx->track[K.kind];
     if (words) HIPCHK(hipMemcpy(words, T.data.p, 4ull * T.channels * T.nBins, hipMemcpyDeviceToHost));
-    if (stats) { unsigned long long h[4]; HIPCHK(hipMemcpy(h, T.stats.p, sizeof h, hipMemcpyDeviceToHost)); for (int k = 0; k < 4; k++) stats[k] = h[k]; }
+    if (stats) { unsigned long long h[8]; HIPCHK(hipMemcpy(h, T.stats.p, sizeof h, hipMemcpyDeviceToHost)); for (uint32_t k = 0; k < K.nStats; k++) stats[k] = h[k]; }
     return 0;
 }
 int ygpu_depth_enable(ygpu_ctx *ctx, const ygpu_depth_params *p)
@@ -325,6 +344,92 @@ int ygpu_events_enable(ygpu_ctx *ctx, const ygpu_events_params *p)
 }
 int ygpu_events_size(ygpu_ctx *ctx, uint64_t *n_bins) { return trackSize(ctx, kEventsKind, n_bins); }
 int ygpu_events_collect(ygpu_ctx *ctx, uint32_t *counts, uint64_t stats[4]) { return trackCollect(ctx, kEventsKind, counts, stats); }
+int ygpu_pileup_enable(ygpu_ctx *ctx, const ygpu_pileup_params *p)
+{
+    return p ? trackEnable(ctx, kPileupKind, 1, p->min_mapq, 0, p->n_seqs, p->seq_start, p->seq_length) : YGPU_EINVAL;
+}
+int ygpu_pileup_size(ygpu_ctx *ctx, uint64_t *n_slots) { return trackSize(ctx, kPileupKind, n_slots); }
+int ygpu_pileup_collect(ygpu_ctx *ctx, uint32_t *counts, uint64_t stats[5]) { return trackCollect(ctx, kPileupKind, counts, stats); }
+// The candidates of the image's array as it stands -- the slots with nonref >= 1, ascending -- selected on the device (pileup_stage.h): count a tile, exclusive
+// sums of the tiles' counts, emit; on the post-filter's side of the context (its stream and look-back words), once everything queued on the device has finished.
+// A PARKED context may be asked as well (the command line's feeder of an image has always run a batch, but a caller may hold any sibling): ygpu_park released
+// that side's counter words with the arenas, so they are made again here -- the look-back words come back by themselves (prims.hip).
+static int pileupSide(ygpu_ctx *full)
+{
+    PfSide *ctx = &full->pf;
+    if (ctx->counters.p) return 0;
+    ENSURE(ctx->counters, 4 * CNT_N);
+    HIPCHK(hipMemsetAsync(ctx->counters.p, 0, 4 * CNT_N, ctx->stream));
+    return 0;
+}
+int ygpu_pileup_candidates_size(ygpu_ctx *full, uint64_t *n)
+{
+    if (!full || !full->stream || !n) return YGPU_EINVAL;
+    if (!full->track[TRACK_PILEUP]) { full->err = "ygpu_pileup_candidates_size: ygpu_pileup_enable has not been called on this context"; return YGPU_EINVAL; }
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    HIPCHK(hipDeviceSynchronize());
+    const TrackImage &T = *full->track[TRACK_PILEUP];
+    full->puHaveCand = false; full->puNCand = 0;
+    int rc = pileupSide(full); if (rc) return rc;
+    const uint32_t nSlots = (uint32_t)T.nBins, nTiles = (uint32_t)((T.nBins + YP_TILE - 1) / YP_TILE);
+    ENSURE(full->puTileCnt, 4ull * (nTiles + 2)); ENSURE(full->puTileStart, 4ull * (nTiles + 2));
+    HIPCHK(hipMemsetAsync((uint32_t *)full->puTileCnt.p + nTiles, 0, 8, ctx->stream));
+    CandidateArgs A; A.L = trackLayout(T); A.pu = T.data.as<uint32_t>(); A.nSlots = nSlots; A.nTiles = nTiles;
+    A.bases = full->dBases.as<uint8_t>(); A.nBaseBytes = full->dBases.cap;
+    A.cnt = full->puTileCnt.as<uint32_t>(); A.start = full->puTileStart.as<uint32_t>(); A.out = nullptr; A.cap = 0;
+    const dim3 grid(gridFor((uint64_t)nTiles * 64, 256));
+    KL(k_pileup_count, grid, dim3(256), 0, ctx->stream, A);
+    rc = cubScan(ctx, full->puTileCnt.as<uint32_t>(), full->puTileStart.as<uint32_t>(), nTiles + 1); if (rc) return rc;
+    uint32_t tot = 0, scanFail = 0;
+    { const FetchPiece pc[2] = {{full->puTileStart.as<uint32_t>() + nTiles, &tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1}};
+      rc = fetchMany(ctx, pc, 2); if (rc) return rc; }
+    if (scanFail) return scanGaveUp(ctx, "pileup candidates");
+    ENSURE(full->puCand, 4ull * ((uint64_t)tot + 1));
+    A.out = full->puCand.as<uint32_t>(); A.cap = tot;
+    if (tot) KL(k_pileup_emit, grid, dim3(256), 0, ctx->stream, A);
+    HIPCHK(streamSync(ctx));
+    tlsPfFailed = nullptr;
+    full->puNCand = tot; full->puHaveCand = true; *n = tot;
+    return 0;
+}
+int ygpu_pileup_candidates_collect(ygpu_ctx *full, uint32_t *slots)
+{
+    if (!full || !full->stream) return YGPU_EINVAL;
+    if (!full->puHaveCand) { full->err = "ygpu_pileup_candidates_collect: ygpu_pileup_candidates_size has not been called on this context"; return YGPU_EINVAL; }
+    if (!full->puNCand) return 0;
+    if (!slots) return YGPU_EINVAL;
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    HIPCHK(hipMemcpyAsync(slots, full->puCand.p, 4ull * full->puNCand, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
+    tlsPfFailed = nullptr;
+    return 0;
+}
+// rows[i][ch] of the image's array for a caller's slots, a piece of the list at a time (the list and its rows pass through buffers of the context)
+int ygpu_pileup_gather(ygpu_ctx *full, const uint32_t *slots, uint64_t n, uint32_t *rows)
+{
+    if (!full || !full->stream || (n && (!slots || !rows))) return YGPU_EINVAL;
+    if (!full->track[TRACK_PILEUP]) { full->err = "ygpu_pileup_gather: ygpu_pileup_enable has not been called on this context"; return YGPU_EINVAL; }
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    HIPCHK(hipDeviceSynchronize());
+    const TrackImage &T = *full->track[TRACK_PILEUP];
+    const uint64_t piece = 1ull << 22;
+    for (uint64_t at = 0; at < n; at += piece) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(piece, n - at);
+        ENSURE(full->puSlots, 4ull * m); ENSURE(full->puRows, 4ull * ypileup::NCH * m);
+        HIPCHK(hipMemcpyAsync(full->puSlots.p, slots + at, 4ull * m, hipMemcpyHostToDevice, ctx->stream));
+        KL(k_pileup_gather, dim3(gridFor((uint64_t)m * ypileup::NCH, 256)), dim3(256), 0, ctx->stream, T.data.as<uint32_t>(), (uint32_t)T.nBins,
+            full->puSlots.as<uint32_t>(), m, full->puRows.as<uint32_t>());
+        HIPCHK(hipMemcpyAsync(rows + at * ypileup::NCH, full->puRows.p, 4ull * ypileup::NCH * m, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(streamSync(ctx));
+    }
+    tlsPfFailed = nullptr;
+    return 0;
+}
 // ---- split-read junctions (junction_stage.h; the contract is in ../junction_core.h) --------------------------------------------------------------------------
 // Per batch and per context, unlike the binned tracks above: the junctions of the batch the context's last ygpu_postfilter filtered.
 int ygpu_junctions_enable(ygpu_ctx *ctx, const ygpu_junction_params *p)

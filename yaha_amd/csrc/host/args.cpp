@@ -3,7 +3,8 @@
 // `yaha -g genome.fa` / `yaha -x index -q reads ...` keep working unchanged.  Extra options of this
 // implementation: -gpus N (shard batches over N devices), -ctx M (contexts per device), -device D, -batch N (reads per device batch),
 // -ocov FILE / -covbin B / -covq Q (read depth of the printed records as bedGraph), -oev FILE / -evbin B / -evq Q / -evclip N (their mismatches, indels and
-// clipped ends per bin), -obp FILE / -bpq Q / -bpw W (split-read breakpoint calls as BEDPE).
+// clipped ends per bin), -obp FILE / -bpq Q / -bpw W (split-read breakpoint calls as BEDPE), -opu FILE / -pumin N / -puq Q (the allele pileup: the sites where
+// at least N reads disagree with the reference, with the counts of A C G T N del ins).
 #include "yaha_host.h"
 #include <cstring>
 #include <cstdlib>
@@ -39,7 +40,14 @@ static void usage(FILE *o)
           "       junction per neighbouring pair (made on the device behind its post-filter); junctions of the same sequences and strands within -bpw bases\n"
           "       of a cluster's first member on both sides are one cluster.  One BEDPE line per cluster, written after the last alignment: chromA, startA,\n"
           "       endA, chromB, startB, endB, type (DEL, DUP, INV, TRA), supporting junctions, strandA, strandB, least and largest gap on the read (negative:\n"
-          "       the pieces overlap).\n", o);
+          "       the pieces overlap).\n"
+          "  pileup  : [-opu sitesFile|stdout] [-pumin minDisagreeingReads (2)] [-puq minMapQ (0)]\n"
+          "       which base the printed records carry at every reference base (A C G T N, deleted, an insertion before it), and the sites where at least -pumin\n"
+          "       of them disagree with the reference: tab-separated with a header line -- chrom, start (0-based), end = start + 1, ref, A, C, G, T, N, del, ins --\n"
+          "       in index order, written after the last alignment.  Accumulated on the device like the depth, per reference base: 28 bytes of device memory per\n"
+          "       reference base per GPU, which is 86.8 GB at 3.1 Gbp; the sites are selected on the device and only they leave it.  When the array does not fit\n"
+          "       the run stops before the first batch and says so (use a smaller -ctx).  The host keeps counts only for the records it counts itself, in blocks\n"
+          "       of 4096 reference bases (112 KB each) made when first touched.  Errors in these three options leave with exit code 3 (the other tracks': 2).\n", o);
 }
 
 static bool parseBool(const char *s, const char *key, bool &out)
@@ -60,6 +68,10 @@ static bool parseFloat(const char *s, const char *key, float &out)
         }
     return true;
 }
+
+// (parseArgs returns the exit code + 1: the pileup's argument errors leave with 3 -- as its specification asks, and as the usage text says; the older tracks'
+// leave with 2)
+static const int kPileupError = 4;
 
 int parseArgs(int argc, char **argv, Args &a)
 {
@@ -132,6 +144,11 @@ int parseArgs(int argc, char **argv, Args &a)
             if (a.bpMinQ < 0 || a.bpMinQ > 255) { fprintf(stderr, "-bpq must be a mapping quality (0 to 255).\n\n"); usage(stderr); return 3; } }
         else if (is("-bpw")) { if (!parseInt(val(), "-bpw", a.bpWindow)) return 3; a.haveBpW = true;
             if (a.bpWindow < 0) { fprintf(stderr, "-bpw must not be negative (bases).\n\n"); usage(stderr); return 3; } }
+        else if (is("-opu")) { const char *v = val(); a.puFileName = (!strcmp(v, "-stdout")) ? "stdout" : v; a.havePu = true;
+            if (a.puFileName.empty()) { fprintf(stderr, "-opu needs a file name.\n\n"); usage(stderr); return kPileupError; } }
+        else if (is("-pumin")) { if (!parseInt(val(), "-pumin", a.puMinAlt)) return kPileupError; a.havePuMin = true;
+            if (a.puMinAlt < 1) { fprintf(stderr, "-pumin must be at least 1 (reads that disagree with the reference).\n\n"); usage(stderr); return kPileupError; } }
+        else if (is("-puq")) { if (!parseInt(val(), "-puq", a.puMinQ)) return kPileupError; a.havePuQ = true; }
         else { fprintf(stderr, "%s is not a valid option.\n\n", k); usage(stderr); return 2; }
     }
     a.query = query; a.index = index && !query;
@@ -154,6 +171,13 @@ int parseArgs(int argc, char **argv, Args &a)
         fprintf(stderr, "-obp stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
     if (a.haveBp && a.bpFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout"))) {
         fprintf(stderr, "-obp stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
+    // the allele pileup: the same rules, its errors with an exit code of their own (3)
+    if (!a.havePu && (a.havePuMin || a.havePuQ)) { fprintf(stderr, "-pumin and -puq need -opu.\n\n"); usage(stderr); return kPileupError; }
+    if (a.havePu && !query) { fprintf(stderr, "-opu is an output of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return kPileupError; }
+    if (a.havePu && a.puFileName == "stdout" && (!a.haveO || a.ofileName == "stdout")) {
+        fprintf(stderr, "-opu stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
+    if (a.havePu && a.puFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout") || (a.haveBp && a.bpFileName == "stdout"))) {
+        fprintf(stderr, "-opu stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
     if ((a.compress || a.uncompress) && !query) {                                                  // Main.c:472-533: -c wants a FASTA genome, -u a .nib2
         if (!a.haveG) { fprintf(stderr, "Genome file specification (-g) is required for index creation.\n\n"); usage(stderr); return 2; }
         size_t dot = a.gfileName.rfind('.'); const std::string ext = dot == std::string::npos ? "" : a.gfileName.substr(dot);
@@ -222,6 +246,7 @@ std::string samHeader(const Args &a, const Genome &g)                   // outpu
     if (a.haveCov) { snprintf(buf, sizeof buf, " -covbin %d -covq %d", a.covBin, a.covMinQ); h += " -ocov " + a.covFileName + buf; }
     if (a.haveEv) { snprintf(buf, sizeof buf, " -evbin %d -evq %d -evclip %d", a.evBin, a.evMinQ, a.evMinClip); h += " -oev " + a.evFileName + buf; }
     if (a.haveBp) { snprintf(buf, sizeof buf, " -bpq %d -bpw %d", a.bpMinQ, a.bpWindow); h += " -obp " + a.bpFileName + buf; }
+    if (a.havePu) { snprintf(buf, sizeof buf, " -pumin %d -puq %d", a.puMinAlt, a.puMinQ); h += " -opu " + a.puFileName + buf; }
     h += "\n";
     return h;
 }

@@ -24,6 +24,11 @@ bool BinnedTrack::init(const Genome &g, int binBases, int minQ, std::string &err
     binBase.assign(seqStart.size() + 1, 0);
     if (binBases < 1 || !ydepth::layoutBins(seqLength.data(), (uint32_t)seqLength.size(), bin, binBase.data(), &nBins)) {
         err = std::string(names.binOpt) + ": the bins do not fit 32 bits"; return false; }
+    return allocate(err);
+}
+
+bool BinnedTrack::allocate(std::string &err)
+{
     free(data); data = (uint32_t *)calloc((nBins ? nBins : 1) * channels, sizeof(uint32_t));      // (untouched pages stay unmapped: a sparse track costs what it holds)
     if (!data) { char m[160]; snprintf(m, sizeof m, "%s: no host memory for %llu bins (%.2f GB)", names.fileOpt, (unsigned long long)nBins, 4.0 * channels * nBins / 1e9);
         err = m; return false; }
@@ -52,6 +57,12 @@ int BinnedTrack::deviceCollect(ygpu_ctx *ctx, std::string &err)
     return 0;
 }
 
+int BinnedTrack::mergeDevices(ygpu_ctx *const *feeders, int n, const Genome &, int *failed, std::string &err)
+{
+    for (int k = 0; k < n; k++) { const int rc = deviceCollect(feeders[k], err); if (rc != 0) { *failed = k; return rc; } }
+    return 0;
+}
+
 uint64_t BinnedTrack::sum() const { uint64_t t = 0; for (uint64_t w = 0; w < nBins * channels; w++) t += data[w]; return t; }
 
 bool BinnedTrack::write(const char *path, const Genome &g, std::string &err) const
@@ -68,7 +79,7 @@ bool BinnedTrack::write(const char *path, const Genome &g, std::string &err) con
 // ---- read depth -----------------------------------------------------------------------------------------------------------------------------------------
 DepthTrack::DepthTrack() : BinnedTrack({"-covbin", "-ocov", "coverage", "depth"}, 1, ygpu_depth_enable != nullptr, ygpu_depth_size, ygpu_depth_collect) {}
 
-void DepthTrack::add(const OutClump &oc, int)
+void DepthTrack::add(const OutClump &oc, const Read &)
 {
     uint32_t *const c = data; const uint64_t n = nBins;
     countRecord(ydepth::walkClump(layout(), oc.c, oc.ops, oc.mapQuality, [c, n](uint32_t b, uint32_t k) { if (b < n) __atomic_fetch_add(c + b, k, __ATOMIC_RELAXED); }, nullptr));

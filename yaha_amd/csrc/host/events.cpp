@@ -21,10 +21,10 @@ EventsTrack::EventsTrack(int minClipBases)
     : BinnedTrack({"-evbin", "-oev", "evidence", "events"}, (uint32_t)yevents::NCH, ygpu_events_enable != nullptr, ygpu_events_size, ygpu_events_collect),
       minClip((uint32_t)minClipBases) {}
 
-void EventsTrack::add(const OutClump &oc, int qlen)
+void EventsTrack::add(const OutClump &oc, const Read &r)
 {
     uint32_t *const e = data; const uint64_t n = nBins;
-    countRecord(yevents::walkClump(layout(), minClip, oc.c, oc.ops, (uint32_t)qlen, oc.mapQuality,
+    countRecord(yevents::walkClump(layout(), minClip, oc.c, oc.ops, (uint32_t)r.len(), oc.mapQuality,
         [e, n](uint32_t b, uint32_t ch, uint32_t k) { if (b < n && ch < (uint32_t)yevents::NCH) __atomic_fetch_add(e + (size_t)b * yevents::NCH + ch, k, __ATOMIC_RELAXED); }));
 }
 

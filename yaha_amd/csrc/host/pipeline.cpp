@@ -26,7 +26,7 @@ struct yaha_session {
     std::vector<uint32_t> pfThr;                                     // the break point table yaha_session_postfilter_params points into
     std::vector<Read> reads; std::vector<uint8_t> codes; std::vector<uint64_t> offsets;
     bool readerOpen = false;
-    std::vector<BinnedTrack *> tracks;                               // -ocov, -oev (the command line): the formatters add the records the device did not count
+    std::vector<BinnedTrack *> tracks;                               // -ocov, -oev, -opu (the command line): the formatters add the records the device did not count
     // -obp: the formatters make the junctions of the reads the device did not (junctions.cpp) into the batch's own list; their counts of the batch
     const JunctionTrack *junctions = nullptr; std::vector<ygpu_junction> *jnOut = nullptr; uint64_t jnReads = 0, jnSkipped = 0;
 };
@@ -139,7 +139,7 @@ enum : unsigned { kJunctionsOnDevice = 1u << 31 };
 static inline void emitRecord(yaha_session *s, uint32_t i, const OutClump &o, int primaryCount, Text &text, unsigned onDevice = 0)
 {
     printClump(s->args, s->genome, s->reads[i], o, primaryCount, text);
-    for (size_t t = 0; t < s->tracks.size(); t++) if (!(onDevice >> t & 1u)) s->tracks[t]->add(o, s->reads[i].len());
+    for (size_t t = 0; t < s->tracks.size(); t++) if (!(onDevice >> t & 1u)) s->tracks[t]->add(o, s->reads[i]);
 }
 static void formatRange(yaha_session *s, const ygpu_result_batch *r, uint32_t i0, uint32_t i1, Text &text, std::vector<OutClump> &oc)
 {
@@ -240,9 +240,9 @@ int runQueries(Args &a, FILE *log)
     // while one context's batch is in a latency-bound device stage the others'
     // batches compute).  Contexts of one device share its index image.
     const int perDev = std::max(1, A.ctxPerGpu), nDev = std::max(1, A.gpus), ngpu = nDev * perDev;
-    // The run's binned tracks (depth.cpp, events.cpp), one table entry each: the host's array, what it is made with, its file, the switch that keeps it on the
+    // The run's binned tracks (depth.cpp, events.cpp, pileup.cpp), one table entry each: the host's array, what it is made with, its file, the switch that keeps it on the
     // host, its keys of the stats line.  The device stage behind the post-filter feeds an array of its own per index image, enabled by every context of the image
-    // (the first makes it) and merged at the end: feeder[k] = 1 + a context of device k that feeds it.  Without the entry points (a build without them), with the
+    // (the first makes it) and merged at the end: feeder[k] = 1 + a context of device k that fed it with a batch.  Without the entry points (a build without them), with the
     // switch set, or when the stage is refused, the formatters count everything.  Track t is bit t of a batch's onDevice mask.
     struct TrackRun { std::unique_ptr<BinnedTrack> track; int binBases, minQ; const std::string *file; const char *hostSwitch, *statsFmt; bool onDevice;
                       std::vector<std::atomic<int>> feeder; };
@@ -251,6 +251,9 @@ int runQueries(Args &a, FILE *log)
         ", \"depth_bins\": %llu, \"depth_device_records\": %llu, \"depth_host_records\": %llu, \"depth_covered_bases\": %llu", false, {}});
     if (A.haveEv) tracks.push_back(TrackRun{std::unique_ptr<BinnedTrack>(new EventsTrack(A.evMinClip)), A.evBin, A.evMinQ, &A.evFileName, "YAHA_HOST_EVENTS",
         ", \"events_bins\": %llu, \"events_device_records\": %llu, \"events_host_records\": %llu, \"events_counted\": %llu", false, {}});
+    // (the allele pileup: a bin of one base, seven channels; its array stays on the device and the end of the run is its own, pileup.cpp)
+    if (A.havePu) tracks.push_back(TrackRun{std::unique_ptr<BinnedTrack>(new PileupTrack(A.puMinAlt)), 1, A.puMinQ, &A.puFileName, "YAHA_HOST_PILEUP",
+        ", \"pileup_bases\": %llu, \"pileup_device_records\": %llu, \"pileup_host_records\": %llu, \"pileup_counted\": %llu", false, {}});
     for (auto &T : tracks) {
         if (!T.track->init(S->genome, T.binBases, T.minQ, S->err)) { fprintf(log, "%s\n", S->err.c_str()); return 1; }
         T.feeder = std::vector<std::atomic<int>>(nDev); for (auto &x : T.feeder) x = 0;
@@ -398,7 +401,7 @@ int runQueries(Args &a, FILE *log)
             // no room for the array beside the image and the arenas: the run stops here, before its first batch, with the sizes (a host array would hide that the
             // device is full; larger bins are the way out).  Any other refusal: this context's records are counted by the formatters.
             if (rcT == YGPU_ENOMEM) { char m[640]; snprintf(m, sizeof m, "%s: %s", tracks[t].track->names.fileOpt, ygpu_last_error(ctx[d])); fail(m); }
-            else if (rcT == 0) { ctxOnDevice |= 1u << t; int none = 0; tracks[t].feeder[d / perDev].compare_exchange_strong(none, d + 1); }
+            else if (rcT == 0) ctxOnDevice |= 1u << t;
         }
         if (rc0 == 0 && junctionsDevice && junctions->deviceEnable(ctx[d]) == 0) ctxOnDevice |= kJunctionsOnDevice;      // (refused: the formatters make this context's)
         if (rc0 != 0) { char m[512];
@@ -496,6 +499,9 @@ int runQueries(Args &a, FILE *log)
                 int rc = ygpu_upload_nowait(ctx[d], &rb); const double h1 = now(); if (rc == 0) rc = ygpu_run(ctx[d]); if (rc != 0) return rc;
                 const double h2 = now();
                 uint64_t nc = 0, no = 0; b->filtered = deviceFilter; b->onDevice = deviceFilter ? ctxOnDevice : 0u;
+                // the image's feeder for the end of the run: the first of its contexts to run a batch -- such a context is never left out (parked) afterwards
+                for (size_t t = 0; t < tracks.size(); t++) if ((b->onDevice >> t & 1u) && tracks[t].feeder[d / perDev].load(std::memory_order_relaxed) == 0) {
+                    int none = 0; tracks[t].feeder[d / perDev].compare_exchange_strong(none, d + 1); }
                 if (!first) { usUpload += (uint64_t)((h1 - h0) * 1e3); usRun += (uint64_t)((h2 - h1) * 1e3); nLater++; }
                 if (deviceFilter && overlapFilter && !first) {                 // the filter thread takes it from here; this thread goes on with the next batch
                     filterIdle();
@@ -603,12 +609,16 @@ int runQueries(Args &a, FILE *log)
     // the binned tracks, in the table's order: every image's array added to the host's, the file written after the last alignment
     for (auto &T : tracks) if (!stop && rcAll == 0) {
         std::string terr; const BinnedTrack::Names &nm = T.track->names;
-        for (int k = 0; k < nDev; k++) if (const int c1 = T.feeder[k].load()) {
-            const int rcT = T.track->deviceCollect(ctx[c1 - 1], terr);
-            if (rcT != 0) { fprintf(log, "%s: collecting the %s array of device %d failed (%d): %s\n", nm.fileOpt, nm.array, devs[k], rcT, terr.c_str()); rcAll = 1; }
-        }
+        std::vector<ygpu_ctx *> feedCtx; std::vector<int> feedDev;
+        for (int k = 0; k < nDev; k++) if (const int c1 = T.feeder[k].load()) { feedCtx.push_back(ctx[c1 - 1]); feedDev.push_back(devs[k]); }
+        const double m0 = now();
+        int failed = -1; const int rcT = T.track->mergeDevices(feedCtx.data(), (int)feedCtx.size(), S->genome, &failed, terr);
+        const double m1 = now();
+        if (rcT != 0) { fprintf(log, "%s: collecting the %s array of device %d failed (%d): %s\n", nm.fileOpt, nm.array, failed >= 0 ? feedDev[failed] : -1, rcT, terr.c_str());
+            rcAll = 1; }
         if (fflush(out) != 0) rcAll = 1;
         if (rcAll == 0 && !T.track->write(T.file->c_str(), S->genome, terr)) { fprintf(log, "%s\n", terr.c_str()); rcAll = 1; }
+        if (timing) fprintf(stderr, "[yaha] %s: devices merged in %.1f ms%s, file written in %.1f ms\n", nm.fileOpt, m1 - m0, T.track->mergeNote().c_str(), now() - m1);
     }
     // the breakpoint calls: the run's junctions clustered and written, after the tracks
     uint64_t nJunctions = 0;
@@ -632,7 +642,8 @@ int runQueries(Args &a, FILE *log)
         char dstat[768] = "";
         for (auto &T : tracks) { const size_t at = strlen(dstat); const BinnedTrack &t = *T.track;
             snprintf(dstat + at, sizeof dstat - at, T.statsFmt, (unsigned long long)t.nBins, (unsigned long long)t.devRecords, (unsigned long long)t.hostRecords,
-                (unsigned long long)t.sum()); }
+                (unsigned long long)t.sum());
+            const std::string more = t.extraStats(); const size_t at2 = strlen(dstat); snprintf(dstat + at2, sizeof dstat - at2, "%s", more.c_str()); }
         if (junctions) { const size_t at = strlen(dstat);
             snprintf(dstat + at, sizeof dstat - at, ", \"bp_device_reads\": %llu, \"bp_host_reads\": %llu, \"bp_junctions\": %llu, \"bp_clusters\": %llu",
                 (unsigned long long)junctions->devReads, (unsigned long long)junctions->hostReads, (unsigned long long)nJunctions, (unsigned long long)junctions->nClusters); }
@@ -706,6 +717,12 @@ int yaha_session_events_params(yaha_session *s, ygpu_events_params *p)
     if (!s || !p) return YGPU_EINVAL;
     p->bin = (uint32_t)s->args.evBin; p->min_mapq = (uint32_t)s->args.evMinQ; p->min_clip = (uint32_t)s->args.evMinClip; p->n_seqs = (uint32_t)s->seqStart.size();
         p->seq_start = s->seqStart.data(); p->seq_length = s->seqLen.data();
+    return 0;
+}
+int yaha_session_pileup_params(yaha_session *s, ygpu_pileup_params *p)
+{
+    if (!s || !p) return YGPU_EINVAL;
+    p->min_mapq = (uint32_t)s->args.puMinQ; p->n_seqs = (uint32_t)s->seqStart.size(); p->seq_start = s->seqStart.data(); p->seq_length = s->seqLen.data();
     return 0;
 }
 int yaha_session_junction_params(yaha_session *s, ygpu_junction_params *p)

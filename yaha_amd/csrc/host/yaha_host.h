@@ -78,6 +78,8 @@ struct Args {
     bool haveEv = false, haveEvBin = false, haveEvQ = false, haveEvClip = false; std::string evFileName; int evBin = 100, evMinQ = 0, evMinClip = 1;
     // breakpoint calls: -obp FILE (BEDPE, one line a cluster of split-read junctions), -bpq Q (records below this mapping quality join nothing), -bpw W (cluster window)
     bool haveBp = false, haveBpQ = false, haveBpW = false; std::string bpFileName; int bpMinQ = 0, bpWindow = 10;
+    // allele pileup: -opu FILE (the sites where at least -pumin reads disagree with the reference, with the counts of A C G T N del ins), -puq Q
+    bool havePu = false, havePuMin = false, havePuQ = false; std::string puFileName; int puMinAlt = 2, puMinQ = 0;
     bool query = false, index = true, compress = false, uncompress = false;   // -c / -u: .fa -> .nib2 / .nib2 -> .fasta only (Main.c:284-293, non-user builds of the reference)
 };
 void postProcessArgs(Args &a, bool query);                                  // AlignArgs.c:108-169
@@ -142,7 +144,7 @@ struct Text {
 };
 void printClump(const Args &a, const Genome &g, const Read &r, const OutClump &oc, int primaryCount, Text &out);
 
-// ---- the binned tracks: read depth (-ocov) and the evidence track (-oev) (depth.cpp, events.cpp; ../depth_core.h, ../events_core.h) -----------------------
+// ---- the binned tracks: read depth (-ocov), the evidence track (-oev) and the allele pileup (-opu) (depth.cpp, events.cpp, pileup.cpp; ../*_core.h) --------
 // The host's array of a track, in the layout the device uses (one routine a kind, *_core.h): `channels` uint32 a bin, bin-major.  The formatter threads add the
 // records the device did NOT count -- runs whose post-filter stays on the host (-dpf N, -OQC N, YAHA_HOST_OQC=1), the reads the device stage hands back
 // unfiltered, and everything when the library has no device entry points for the track or refuses to enable them -- with relaxed atomics.  At the end of the
@@ -164,22 +166,29 @@ struct BinnedTrack {
     uint64_t devRecords = 0, devSkipped = 0, devDropped = 0, devHandedBack = 0;
     BinnedTrack(const BinnedTrack &) = delete; BinnedTrack &operator=(const BinnedTrack &) = delete;
     virtual ~BinnedTrack() { free(data); }
-    bool init(const Genome &g, int binBases, int minQ, std::string &err);
-    virtual void add(const OutClump &oc, int qlen) = 0;                   // one record printClump was called for, and its read's length
+    bool init(const Genome &g, int binBases, int minQ, std::string &err);    // the layout, then the kind's host storage (allocate)
+    virtual void add(const OutClump &oc, const Read &r) = 0;              // one record printClump was called for, and its read (its length; the pileup: its bases)
     bool deviceEntryPoints() const { return haveEnable && devSize && devCollect; }      // does this build have the kind's ygpu_*_enable / _size / _collect?
     virtual int deviceEnable(ygpu_ctx *ctx) const = 0;                    // YGPU_ENODEV without the entry points
     int  deviceCollect(ygpu_ctx *ctx, std::string &err);                  // adds the image's array and statistics to this track
-    uint64_t sum() const;                                                 // over all bins and channels
+    // The end of the run: what the devices counted joins what the host counted.  feeders[k]: a context of index image k that fed the image's array (n may be 0).
+    // Returns 0, or the device's error code with *failed = the image it came from.  Here: deviceCollect of every image; a kind whose array does not travel
+    // (the pileup) has its own way.
+    virtual int mergeDevices(ygpu_ctx *const *feeders, int n, const Genome &g, int *failed, std::string &err);
+    virtual uint64_t sum() const;                                         // over all bins and channels
+    virtual std::string extraStats() const { return std::string(); }      // more keys of the stats line, each with its leading ", "
+    virtual std::string mergeNote() const { return std::string(); }       // where mergeDevices' time went, for the YAHA_TIMING line
     bool write(const char *path, const Genome &g, std::string &err) const;      // path "stdout" = standard output
   protected:
     BinnedTrack(const Names &nm, uint32_t ch, bool enable, SizeFn sz, CollectFn co) : names(nm), channels(ch), haveEnable(enable), devSize(sz), devCollect(co) {}
     ydepth::Layout layout() const { return ydepth::Layout{seqStart.data(), seqLength.data(), binBase.data(), (uint32_t)seqStart.size(), bin, minMapq}; }
     void countRecord(int gate);                                           // what became of a record the host walked (ydepth::COUNTED ...)
+    virtual bool allocate(std::string &err);                              // the host's storage for nBins bins: here the dense, zeroed `data`
     virtual bool writeLines(FILE *f, const Genome &g) const = 0;          // the kind's lines; false: a write failed
 };
 struct DepthTrack : BinnedTrack {                                         // bedGraph of the covered bases
     DepthTrack();
-    void add(const OutClump &oc, int qlen) override;
+    void add(const OutClump &oc, const Read &r) override;
     int  deviceEnable(ygpu_ctx *ctx) const override;
   protected:
     bool writeLines(FILE *f, const Genome &g) const override;
@@ -187,10 +196,38 @@ struct DepthTrack : BinnedTrack {                                         // bed
 struct EventsTrack : BinnedTrack {                                        // mismatched bases, deleted bases, insertions, clipped ends left and right
     uint32_t minClip = 1;
     explicit EventsTrack(int minClipBases);
-    void add(const OutClump &oc, int qlen) override;
+    void add(const OutClump &oc, const Read &r) override;
     int  deviceEnable(ygpu_ctx *ctx) const override;
   protected:
     bool writeLines(FILE *f, const Genome &g) const override;
+};
+// The allele pileup: A C G T N del ins per reference base (../pileup_core.h), written as the table of the sites where at least minAlt reads disagree with the
+// reference.  Its device array (28 bytes a reference base) never travels: at the end of the run every source -- each index image, the host's own counts --
+// lists its candidates (nonref >= 1), every image gathers its counts at the sorted union, the host adds its own and applies minAlt (mergeDevices).  Nothing
+// dense on the host either: its counts live in blocks of kBlock slots, made when a formatter thread first adds to one (`data` stays null) -- a pointer per
+// block, 6 MB of them at 3.1 Gbp, and 112 KB for every block the host's share of the records touches.
+struct PileupTrack : BinnedTrack {
+    enum : uint32_t { kBlock = 4096 };
+    uint32_t minAlt = 2;
+    std::vector<uint32_t *> blocks;                                       // blocks[slot / kBlock]: kBlock * 7 zeroed words, or null (atomic loads, made by compare-and-swap)
+    uint64_t hostCounted = 0, devCounted = 0, nCandidates = 0;            // counts added by the formatters / on the devices; slots of the union
+    struct Site { uint32_t slot, ref; uint32_t n[7]; };                   // ref: the reference's 4-bit code
+    std::vector<Site> sites;                                              // what writeLines prints, ascending (made by mergeDevices)
+    explicit PileupTrack(int minAltReads);
+    ~PileupTrack() override;
+    void add(const OutClump &oc, const Read &r) override;
+    int  deviceEnable(ygpu_ctx *ctx) const override;
+    int  mergeDevices(ygpu_ctx *const *feeders, int n, const Genome &g, int *failed, std::string &err) override;
+    uint64_t sum() const override { return hostCounted + devCounted; }    // (the counts added: the sum over the arrays without reading 28 bytes a base)
+    std::string extraStats() const override;
+    std::string mergeNote() const override;
+    double msCandidates = 0, msGather = 0;                                // mergeDevices: the selections and their copies / the gathers
+  protected:
+    bool allocate(std::string &err) override;                             // the table of blocks, all null (the bin must be 1)
+    bool writeLines(FILE *f, const Genome &g) const override;
+  private:
+    uint32_t *block(uint32_t slot);                                       // the block of a slot, made if it is not there yet
+    const uint32_t *row(uint32_t slot) const { const uint32_t *b = blocks[slot / kBlock]; return b ? b + (size_t)(slot % kBlock) * 7 : nullptr; }
 };
 
 // ---- split-read breakpoint calls (-obp; junctions.cpp, ../junction_core.h) ---------------------------------------------------------------------------------
