@@ -297,6 +297,39 @@ int  ygpu_pileup_candidates_collect(ygpu_ctx *ctx, uint32_t *slots);           /
 /* rows[n * 7]: the seven counts of slots[0 .. n) (host memory; ascending for locality, not checked; a slot past the array reads as zeros). */
 int  ygpu_pileup_gather(ygpu_ctx *ctx, const uint32_t *slots, uint64_t n, uint32_t *rows);
 
+/* ---- indel alleles: which insertions and deletions the printed alignments carry (optional, behind ygpu_postfilter) -----------------------------------------------
+ * What the pileup's INS and DEL channels leave out: how long an indel is and what was inserted.  With ygpu_indels_enable, every ygpu_postfilter of the context
+ * also counts the indel ALLELES of the clumps it returns in a hash table on the device.  The contract (yaha_amd/csrc/indel_core.h -- one set of routines for
+ * host and device): slots, gates and the two-sequence drop are the pileup's; a D op of at least min_length bases is the allele (slot of its first base, DEL,
+ * length), an I op of at least min_length bases the allele (slot of the next reference base the walk reaches, kept inside the record; INS; length; the first
+ * min(length, 42) inserted bases as channels A0 C1 G2 T3 N4 in reference orientation); an insertion whose bases would lie past the clump's eqo, or a deletion
+ * past its last reference base, is no event; two insertions of more than 42 bases that agree in slot, length and first 42 bases are one allele; a record adds 1
+ * per event.  The key: w0 = slot | type << 32 | length << 33 | 1 << 63, w1 / w2 = 21 bases each at 3 bits, the first lowest, bit 63 set (a deletion: that bit alone).
+ * Reads that come back UNFILTERED (primaryCount == 0xFFFF) are NOT counted: the caller filters them and counts what it prints.
+ * The table is the CONTEXT's own (as the junctions' buffers are, unlike the binned arrays): open addressing, linear probing, `capacity` entries of 32 bytes, a
+ * power of two.  capacity == 0 asks for the rule: the smallest power of two >= 2 x the context's batch capacity in bases -- the bases of the largest batch it
+ * has held, at least 2^20; made at enable and made larger before a larger batch is counted while it is EMPTY (a batch has at most one event per two bases: a
+ * caller that collects whenever ygpu_indels_size says more than capacity / 4 keeps the load at or below one half).  A capacity that is no power of two is
+ * refused.  An event that finds no entry within the probe limit is counted as LOST and ygpu_postfilter answers YGPU_EOVERFLOW, naming -oid in
+ * ygpu_last_error: the filtered batch is lost, the table holds a part of it; after ygpu_indels_collect the context serves its next batch.
+ * While the stage is enabled ygpu_postfilter_snapshot also copies the batch's forward codes and read offsets (as for the pileup), and ygpu_postfilter ends with
+ * one more small wait (the used and lost words).  ygpu_indels_size: entries in use after the context's last ygpu_postfilter.  ygpu_indels_collect: the occupied
+ * entries compacted on the device in ascending table index (count a tile, exclusive sums, emit by ballot), copied to out[ygpu_indels_size] (may be NULL when
+ * that is 0), then the table, the statistics and both words are CLEARED: every entry is returned once.  stats (may be NULL), since the previous collect:
+ * records counted, records skipped (MAPQ), records dropped (two sequences), events, reads left to the caller, events lost.  Both calls use the post-filter's
+ * side of the context: between batches, not while a ygpu_postfilter of the context is running.  A parked context (ygpu_park) has given its table up: 0 entries.
+ * Order: ygpu_set_postfilter, ygpu_indels_enable, then batches (ygpu_run, ygpu_postfilter, now and then ygpu_indels_collect), a last ygpu_indels_collect. */
+#define YGPU_INDEL_KEPT_BASES 42
+typedef struct ygpu_indel_params {
+    uint32_t min_mapq, min_length, n_seqs, reserved;
+    const uint32_t *seq_start, *seq_length;            /* reference sequences in bases, ascending (host memory; copied) */
+    uint64_t capacity;                                 /* entries, a power of two; 0: the rule above */
+} ygpu_indel_params;
+typedef struct ygpu_indel_entry { uint64_t w0, w1, w2; uint32_t count, zero; } ygpu_indel_entry;      /* 32 bytes */
+int  ygpu_indels_enable(ygpu_ctx *ctx, const ygpu_indel_params *p);            /* after ygpu_set_postfilter */
+int  ygpu_indels_size(ygpu_ctx *ctx, uint64_t *used);
+int  ygpu_indels_collect(ygpu_ctx *ctx, ygpu_indel_entry *out, uint64_t stats[6]);
+
 /* ---- split-read breakpoint calls: where the printed alignments of a read join (optional, behind ygpu_postfilter) ----------------------------------------------
  * The primary signal of a structural-variant caller.  With ygpu_junctions_enable, every ygpu_postfilter of the context also makes the JUNCTIONS of its batch on
  * the device.  The contract (yaha_amd/csrc/junction_core.h -- one set of routines for host and device): the eligible records of a read are the printed ones (a
@@ -438,6 +471,8 @@ int  yaha_session_depth_params(yaha_session *s, ygpu_depth_params *p);
 int  yaha_session_events_params(yaha_session *s, ygpu_events_params *p);
 /* The same for ygpu_pileup_enable: -puq (default 0) and the sequence table (pointers of their own into the session). */
 int  yaha_session_pileup_params(yaha_session *s, ygpu_pileup_params *p);
+/* The same for ygpu_indels_enable: -idq (default 0), -idlen (default 1), capacity 0 and the sequence table (pointers of their own into the session). */
+int  yaha_session_indel_params(yaha_session *s, ygpu_indel_params *p);
 /* The same for ygpu_junctions_enable: -bpq (default 0) and the sequence table (pointers of their own into the session). */
 int  yaha_session_junction_params(yaha_session *s, ygpu_junction_params *p);
 /* `yaha -g genome.fa [-L k] [-S s] [-H h]`: writes genome.nib2 and genome.X<LL>_<SS>_<HHHHH>S (Main.c:554-628). */

@@ -94,6 +94,41 @@ PILEUP_CHANNELS = ("A", "C", "G", "T", "N", "del", "ins")
 PILEUP_STATS = DEPTH_STATS + ("counts_added",)
 
 
+class IndelParams(C.Structure):
+    _fields_ = [("min_mapq", C.c_uint32), ("min_length", C.c_uint32), ("n_seqs", C.c_uint32), ("reserved", C.c_uint32), ("seq_start", C.c_void_p), ("seq_length", C.c_void_p),
+                ("capacity", C.c_uint64)]
+
+
+class IndelEntry(C.Structure):
+    """One allele of the device's table: the key's three words (yaha_amd/csrc/indel_core.h) and the records that carry it."""
+    _fields_ = [("w0", C.c_uint64), ("w1", C.c_uint64), ("w2", C.c_uint64), ("count", C.c_uint32), ("zero", C.c_uint32)]
+
+    INS_KEPT = 42
+
+    @property
+    def slot(self):
+        return self.w0 & 0xFFFFFFFF
+
+    @property
+    def type(self):
+        return "INS" if (self.w0 >> 32) & 1 else "DEL"
+
+    @property
+    def length(self):
+        return (self.w0 >> 33) & 0xFFFF
+
+    @property
+    def bases(self):
+        """The kept bases of an insertion as letters (the first 42), '' for a deletion."""
+        if self.type == "DEL":
+            return ""
+        n = min(self.length, self.INS_KEPT)
+        return "".join("ACGTN"[min(4, ((self.w1 >> (3 * i)) if i < 21 else (self.w2 >> (3 * (i - 21)))) & 7)] for i in range(n))
+
+
+INDEL_STATS = ("records_counted", "records_skipped_mapq", "records_dropped_two_sequences", "events", "reads_left_to_host", "events_lost")
+
+
 class JunctionParams(C.Structure):
     _fields_ = [("min_mapq", C.c_uint32), ("n_seqs", C.c_uint32), ("seq_start", C.c_void_p), ("seq_length", C.c_void_p)]
 
@@ -129,6 +164,7 @@ EXPORTS = (
     "ygpu_events_enable", "ygpu_events_size", "ygpu_events_collect", "yaha_session_events_params",
     "ygpu_pileup_enable", "ygpu_pileup_size", "ygpu_pileup_collect", "ygpu_pileup_candidates_size", "ygpu_pileup_candidates_collect", "ygpu_pileup_gather",
     "yaha_session_pileup_params",
+    "ygpu_indels_enable", "ygpu_indels_size", "ygpu_indels_collect", "yaha_session_indel_params",
     "ygpu_junctions_enable", "ygpu_junctions_size", "ygpu_junctions_collect", "yaha_session_junction_params",
     "ygpu_submit", "ygpu_poll", "ygpu_wait", "ygpu_seed_join", "ygpu_chain", "ygpu_dp_batch", "ygpu_dp_batch_ex",
     "yaha_session_open", "yaha_session_close", "yaha_session_error", "yaha_session_params",
@@ -369,6 +405,27 @@ class Context:
         self._check(lib().ygpu_pileup_gather(self._h, sl.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_uint64(len(sl)), rows.ctypes.data_as(C.POINTER(C.c_uint32))),
                     "ygpu_pileup_gather")
         return rows[:len(sl)]
+
+    def indels_enable(self, session, capacity=0):
+        """Indel alleles of the printed clumps behind postfilter() (ygpu_indels_enable), counted in a hash table of this context's own, with the session's -idq,
+        -idlen and sequence table.  capacity: entries, a power of two; 0: twice the context's batch capacity in bases.  After set_postfilter()."""
+        p = IndelParams()
+        if lib().yaha_session_indel_params(session._h, C.byref(p)) != 0:
+            raise RuntimeError("yaha_session_indel_params: " + lib().yaha_session_error(session._h).decode())
+        p.capacity = capacity
+        self._check(lib().ygpu_indels_enable(self._h, C.byref(p)), "ygpu_indels_enable")
+
+    def indels_size(self):
+        """Entries of the table in use after the last postfilter() (ygpu_indels_size)."""
+        n = C.c_uint64()
+        self._check(lib().ygpu_indels_size(self._h, C.byref(n)), "ygpu_indels_size")
+        return int(n.value)
+
+    def indels_collect(self):
+        """(the table's occupied entries in ascending table index -- a list of IndelEntry -- and the statistics since the previous collect as a dict); the
+        table is empty afterwards (ygpu_indels_collect)."""
+        out, n, st = self._collect(lib().ygpu_indels_size, lib().ygpu_indels_collect, lambda n: ((IndelEntry * max(1, n))(),) * 2, INDEL_STATS)
+        return [out[i] for i in range(n)], st
 
     def junctions_enable(self, session):
         """Split-read junctions of every batch behind postfilter() (ygpu_junctions_enable), with the session's -bpq and sequence table.  After set_postfilter()."""

@@ -363,7 +363,8 @@ std::vector<DevBuf *> allBuffers(ygpu_ctx *ctx)
                              &ctx->oqThr, &ctx->oqSeqStart, &ctx->oqSeqLen, &ctx->oqNeed, &ctx->oqPoolOff, &ctx->oqKeys, &ctx->oqStack, &ctx->oqNodes, &ctx->oqPrim, &ctx->oqPA,
                              &ctx->oqPfx, &ctx->oqPath, &ctx->oqPool, &ctx->oqPush, &ctx->oqOut, &ctx->oqOutCnt, &ctx->oqOutOps, &ctx->oqPrimCnt, &ctx->oqOutStart,
                              &ctx->oqOpsStart, &ctx->oqFClumps, &ctx->oqFOps, &ctx->jnCnt, &ctx->jnStart, &ctx->jnOut, &ctx->jnStats, &ctx->jnSeqStart, &ctx->jnSeqLen,
-                         &ctx->puFwd, &ctx->puReadOff, &ctx->puTileCnt, &ctx->puTileStart, &ctx->puCand, &ctx->puSlots, &ctx->puRows};
+                         &ctx->puFwd, &ctx->puReadOff, &ctx->puTileCnt, &ctx->puTileStart, &ctx->puCand, &ctx->puSlots, &ctx->puRows,
+                         &ctx->idTable, &ctx->idStats, &ctx->idSeqStart, &ctx->idSeqLen, &ctx->idBinBase, &ctx->idTileCnt, &ctx->idTileStart, &ctx->idOut};
     return std::vector<DevBuf *>(all, all + sizeof all / sizeof all[0]);
 }
 extern "C" {
@@ -417,7 +418,7 @@ int ygpu_park(ygpu_ctx *ctx)
     HIPCHK(hipSetDevice(ctx->device)); HIPCHK(streamSync(ctx));
     for (DevBuf *b : allBuffers(ctx)) if (b != &ctx->dBases && b != &ctx->dSO && b != &ctx->dROA && b != &ctx->dLow) b->release();
     if (ctx->counted) { gCtxPerDevice[ctx->device & 63]--; ctx->counted = false; }
-    ctx->stageDone = 0; ctx->parked = true;
+    ctx->stageDone = 0; ctx->parked = true; ctx->idUsed = 0;
     return 0;
 }
 /* What a context's arenas hold after a batch, and the estimates it carries from batch to batch -- so that the device's other contexts can be given the same
@@ -444,7 +445,7 @@ int ygpu_presize(ygpu_ctx *ctx, const ygpu_arena_profile *prof)
     for (size_t k = 0; k < all.size(); k++) {
         DevBuf *b = all[k];
         if (b == &ctx->dBases || b == &ctx->dSO || b == &ctx->dROA || b == &ctx->dLow || b == &ctx->counters || b == &ctx->ctr || b == &ctx->errFlag
-            || b == &ctx->pf.counters) continue;
+            || b == &ctx->pf.counters || b == &ctx->idTable || b == &ctx->idStats) continue;      // (the indel table is made, and zeroed, by its enable alone)
         if (prof->cap[k] > b->cap && b->ensureExact((size_t)prof->cap[k])) { (void)hipGetLastError(); ctx->err = "hipMalloc failed while presizing the arenas"; return YGPU_ENOMEM;
             }
     }

@@ -211,6 +211,14 @@ struct ygpu_ctx {
     // candidate slots, a caller's slot list and the rows gathered for it
     DevBuf puFwd, puReadOff, puTileCnt, puTileStart, puCand, puSlots, puRows;
     uint64_t puNCand = 0; bool puHaveCand = false;
+    // indel alleles (-oid; indel_stage.h, ../indel_core.h): the context's own hash table (idCap entries of 32 bytes, a power of two; idAuto: sized by the rule and
+    // made larger, while empty, before a larger batch), its statistics (eight 64-bit words, then the used and the lost word), the sequence table and slot bases
+    // of its layout, and for draining the occupied entries per tile, their exclusive sums and the compacted entries.  The stage reads the bases from puFwd /
+    // puReadOff, which the snapshot then copies as for the pileup.  idUsed: entries in use after the last ygpu_postfilter (0 after a collect).
+    DevBuf idTable, idStats, idSeqStart, idSeqLen, idBinBase, idTileCnt, idTileStart, idOut;
+    bool idSet = false, idAuto = false;
+    uint64_t idCap = 0, snapBases = 0;
+    uint32_t idMinMapq = 0, idMinLen = 1, idNSeqs = 0, idUsed = 0;
     // split-read junctions (-obp; junction_stage.h, ../junction_core.h): made per batch behind the post-filter, in buffers of the context's own -- counts and
     // their exclusive sums per read, the junctions (sized from the batch's filtered clump count), four statistics words, a sequence table of their own
     DevBuf jnCnt, jnStart, jnOut, jnStats, jnSeqStart, jnSeqLen;

@@ -2,12 +2,14 @@
 // GraphPath.cpp:897-1086, Query.c:450) on a snapshot of them -- oqc_stage.h -- with its own stream, wait slot and look-back words (PfSide); behind it, when
 // ygpu_depth_enable asked for it, the read-depth track of the printed clumps (depth_stage.h), and when ygpu_events_enable did, their evidence track
 // (events_stage.h), and when ygpu_pileup_enable did, their allele pileup (pileup_stage.h: the one track that reads the reads' bases, which the snapshot then copies
-// as well); and when ygpu_junctions_enable did, the batch's split-read junctions (junction_stage.h), which leave with the filtered batch.
+// as well), and when ygpu_indels_enable did, their indel alleles in the context's own hash table (indel_stage.h); and when ygpu_junctions_enable did, the
+// batch's split-read junctions (junction_stage.h), which leave with the filtered batch.
 #include "ctx.h"
 #include "oqc_stage.h"
 #include "depth_stage.h"
 #include "events_stage.h"
 #include "pileup_stage.h"
+#include "indel_stage.h"
 #include "junction_stage.h"
 #include <map>
 #include <tuple>
@@ -84,8 +86,10 @@ int ygpu_postfilter_snapshot(ygpu_ctx *ctx)
     if (n) KL(k_oqc_seeds, dim3(gridFor(n, 256)), dim3(256), 0, ctx->stream, ctx->dFwd.as<uint8_t>(), ctx->dReadOff.as<uint32_t>(), n, ctx->oqSeeds.as<uint32_t>(),
         ctx->oqQlen.as<uint32_t>());
     // the allele pileup reads the reads' bases behind the filter, when the next upload may have overwritten them: the forward codes (the reverse strand's channel
-    // follows from them, pileup_core.h) and the reads' offsets join the snapshot -- only on a context that enabled the pileup
-    if (ctx->track[TRACK_PILEUP] && n) {
+    // follows from them, pileup_core.h) and the reads' offsets join the snapshot -- only on a context that enabled the pileup or the indel alleles, which read
+    // the inserted bases there
+    ctx->snapBases = ctx->totalBases;
+    if ((ctx->track[TRACK_PILEUP] || ctx->idSet) && n) {
         ENSURE(ctx->puFwd, ctx->totalBases + 1); ENSURE(ctx->puReadOff, 4ull * (n + 1));
         if (ctx->totalBases) HIPCHK(hipMemcpyAsync(ctx->puFwd.p, ctx->dFwd.p, ctx->totalBases, hipMemcpyDeviceToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(ctx->puReadOff.p, ctx->dReadOff.p, 4ull * (n + 1), hipMemcpyDeviceToDevice, ctx->stream));
@@ -115,6 +119,25 @@ static ydepth::Layout trackLayout(const TrackImage &T)
 {
     return ydepth::Layout{T.seqStart.as<uint32_t>(), T.seqLength.as<uint32_t>(), T.binBase.as<uint32_t>(), (uint32_t)T.hSeqStart.size(), T.bin, T.minMapq};
 }
+static ydepth::Layout indelLayout(const ygpu_ctx *full)
+{
+    return ydepth::Layout{full->idSeqStart.as<uint32_t>(), full->idSeqLen.as<uint32_t>(), full->idBinBase.as<uint32_t>(), full->idNSeqs, 1u, full->idMinMapq};
+}
+// the indel table made (or made again, larger) and zeroed with its statistics, on the post-filter side's stream
+static int indelTable(ygpu_ctx *full, uint64_t capacity)
+{
+    PfSide *ctx = &full->pf;
+    if (full->idTable.ensureExact(sizeof(ygpu_indel_entry) * capacity)) {
+        (void)hipGetLastError(); size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) != hipSuccess) { fb = 0; (void)hipGetLastError(); }
+        char m[256]; snprintf(m, sizeof m, "ygpu_indels_enable: no room on device %d for the indel table (-oid): %.2f GB for %llu entries, %.2f GB free", full->device,
+            sizeof(ygpu_indel_entry) * capacity / 1e9, (unsigned long long)capacity, fb / 1e9);
+        ctx->err = m; full->err = m; full->idCap = 0; return YGPU_ENOMEM;
+    }
+    full->idCap = capacity; full->idUsed = 0;
+    HIPCHK(hipMemsetAsync(full->idTable.p, 0, sizeof(ygpu_indel_entry) * capacity, ctx->stream));
+    HIPCHK(hipMemsetAsync(full->idStats.p, 0, 128, ctx->stream));
+    return 0;
+}
 // The binned tracks of the nClumps clumps just gathered -- the ones that get printed -- on the post-filter's stream, a wave a clump: the evidence track (the wave
 // finds its clump's read -- the query length of the right clip -- in oqOutStart; YGPU_EVENTS_DIRECT: every op's atomics without the combining in the wave, for
 // measurements; read at every call), then read depth and its count of the reads handed back, then the allele pileup (the wave finds its clump's read the same
@@ -141,6 +164,14 @@ static int launchTracks(ygpu_ctx *full, uint32_t n, uint32_t nClumps)
         PileupArgs P; P.L = trackLayout(*T); P.pu = T->data.as<uint32_t>(); P.nSlots = (uint32_t)T->nBins; P.stats = T->stats.as<unsigned long long>();
         P.fwd = full->puFwd.as<uint8_t>(); P.readOff = full->puReadOff.as<uint32_t>();
         KL(k_pileup_clumps, grid, block, 0, ctx->stream, P, fClumps, fOps, full->oqOutStart.as<uint32_t>(), n, nClumps);
+    }
+    // the indel alleles, behind the pileup's kernel: into the context's own table
+    if (full->idSet && full->idTable.p) {
+        IndelArgs A; A.L = indelLayout(full); A.minLen = full->idMinLen; A.table = full->idTable.as<ygpu_indel_entry>(); A.mask = (uint32_t)(full->idCap - 1);
+        A.probeLimit = (uint32_t)std::min<uint64_t>(full->idCap, YI_PROBE_LIMIT);
+        A.stats = full->idStats.as<unsigned long long>(); A.used = full->idStats.as<uint32_t>() + 16; A.lost = A.used + 1;
+        A.fwd = full->puFwd.as<uint8_t>(); A.readOff = full->puReadOff.as<uint32_t>();
+        KL(k_indel_clumps, grid, block, 0, ctx->stream, A, fClumps, fOps, full->oqOutStart.as<uint32_t>(), n, nClumps);
     }
     return 0;
 }
@@ -245,8 +276,18 @@ static int postfilterBody(ygpu_ctx *full)
         KL(k_junction_emit, grid, dim3(256), 0, ctx->stream, J);
         full->jnReads = n; full->jnDone = true;
     }
-    // the binned tracks that are enabled (-oev, -ocov, -opu), behind the junctions on this stage's stream
+    // the indel table by the rule: a batch larger than any before it gets a larger table while the table is empty (a table with entries stays as it is)
+    if (full->idSet && full->idAuto && full->idUsed == 0 && full->idTable.p && yindel::tableCapacity(full->snapBases) > full->idCap) {
+        rc = indelTable(full, yindel::tableCapacity(full->snapBases)); if (rc) return rc; }
+    // the binned tracks that are enabled (-oev, -ocov, -opu) and the indel alleles (-oid), behind the junctions on this stage's stream
     rc = launchTracks(full, n, tot[0]); if (rc) return rc;
+    // the indel table's used and lost words: one more small wait, behind the kernel.  An event that found no entry is an error of this call, not a fault.
+    if (full->idSet && full->idTable.p && tot[0]) {
+        uint32_t ul[2] = {0, 0}; rc = fetchU32(ctx, full->idStats.as<uint32_t>() + 16, ul, 2); if (rc) return rc;
+        full->idUsed = ul[0];
+        if (ul[1]) { char m[256]; snprintf(m, sizeof m, "ygpu_postfilter: %u indel events found no entry in the table of %llu entries, %u of them in use (-oid): "
+            "call ygpu_indels_collect more often or enable a larger capacity", ul[1], (unsigned long long)full->idCap, ul[0]); ctx->err = m; return YGPU_EOVERFLOW; }
+    }
     if (oqProf) {
         unsigned long long h[32 * YQ_NCLASS]; HIPCHK(hipMemcpyAsync(h, full->oqProf.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
         static const char *nm[7] = {"keys", "sort", "dup scan", "nodes+tables", "path walk", "successors", "finish"};
@@ -428,6 +469,87 @@ int ygpu_pileup_gather(ygpu_ctx *full, const uint32_t *slots, uint64_t n, uint32
         HIPCHK(streamSync(ctx));
     }
     tlsPfFailed = nullptr;
+    return 0;
+}
+// ---- indel alleles (indel_stage.h; the contract is in ../indel_core.h) -------------------------------------------------------------------------------------------
+// Per context, as the junctions are: a hash table of the context's own, fed by every ygpu_postfilter, drained by ygpu_indels_collect.
+int ygpu_indels_enable(ygpu_ctx *full, const ygpu_indel_params *p)
+{
+    if (!full || !full->stream || !p) return YGPU_EINVAL;
+    tlsPfFailed = nullptr;
+    if (!full->oqSet) { full->err = "ygpu_indels_enable: ygpu_set_postfilter has not been called on this context (the alleles are counted behind the post-filter)";
+        return YGPU_EINVAL; }
+    if (!p->n_seqs || !p->seq_start || !p->seq_length || p->min_mapq > 255 || p->min_length < 1) {
+        full->err = "ygpu_indels_enable: bad mapping quality, minimum length or sequence table"; return YGPU_EINVAL; }
+    if (p->capacity && ((p->capacity & (p->capacity - 1)) != 0 || p->capacity > (1ull << 31))) {
+        full->err = "ygpu_indels_enable: the capacity must be a power of two of at most 2^31 entries (0: twice the batch capacity in bases)"; return YGPU_EINVAL; }
+    if (full->parked) { full->err = "ygpu_indels_enable: the context was parked (ygpu_park)"; return YGPU_EINVAL; }
+    std::vector<uint32_t> binBase(p->n_seqs + 1); uint64_t nSlots = 0;
+    if (!ydepth::layoutBins(p->seq_length, p->n_seqs, 1, binBase.data(), &nSlots) || nSlots == 0) { full->err = "ygpu_indels_enable: the slots do not fit 32 bits";
+        return YGPU_EINVAL; }
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    HIPCHK(streamSync(ctx));                                                   // (a second enable: nothing of this side may still be using the table)
+    ENSURE(full->idSeqStart, 4ull * p->n_seqs); ENSURE(full->idSeqLen, 4ull * p->n_seqs); ENSURE(full->idBinBase, 4ull * (p->n_seqs + 1)); ENSURE(full->idStats, 128);
+    // the rule: twice the bases of the largest batch the context has held -- what its buffer of forward codes holds -- and at least 2^20 of them
+    const uint64_t capacity = p->capacity ? p->capacity : yindel::tableCapacity(std::max<uint64_t>(1ull << 20, std::max<uint64_t>(full->totalBases, full->snapBases)));
+    full->idSet = false;
+    int rc = indelTable(full, capacity); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(full->idSeqStart.p, p->seq_start, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(full->idSeqLen.p, p->seq_length, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(full->idBinBase.p, binBase.data(), 4ull * (p->n_seqs + 1), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(streamSync(ctx));
+    tlsPfFailed = nullptr;
+    full->idMinMapq = p->min_mapq; full->idMinLen = p->min_length; full->idNSeqs = p->n_seqs; full->idAuto = p->capacity == 0; full->idSet = true;
+    return 0;
+}
+int ygpu_indels_size(ygpu_ctx *ctx, uint64_t *used)
+{
+    if (!ctx || !ctx->stream || !used) return YGPU_EINVAL;
+    if (!ctx->idSet) { ctx->err = "ygpu_indels_size: ygpu_indels_enable has not been called on this context"; return YGPU_EINVAL; }
+    *used = ctx->idTable.p ? ctx->idUsed : 0; return 0;
+}
+int ygpu_indels_collect(ygpu_ctx *full, ygpu_indel_entry *out, uint64_t stats[6])
+{
+    if (!full || !full->stream) return YGPU_EINVAL;
+    tlsPfFailed = nullptr;
+    if (!full->idSet) { full->err = "ygpu_indels_collect: ygpu_indels_enable has not been called on this context"; return YGPU_EINVAL; }
+    if (stats) for (int k = 0; k < 6; k++) stats[k] = 0;
+    if (!full->idTable.p) return 0;                                            // (parked: the table went with the arenas)
+    if (full->idUsed && !out) return YGPU_EINVAL;
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    int rc = pileupSide(full); if (rc) return rc;
+    const uint32_t nTiles = (uint32_t)((full->idCap + YI_TILE - 1) / YI_TILE);
+    ENSURE(full->idTileCnt, 4ull * (nTiles + 2)); ENSURE(full->idTileStart, 4ull * (nTiles + 2));
+    HIPCHK(hipMemsetAsync((uint32_t *)full->idTileCnt.p + nTiles, 0, 8, ctx->stream));
+    IndelDrainArgs A; A.table = full->idTable.as<ygpu_indel_entry>(); A.capacity = full->idCap; A.nTiles = nTiles; A.cnt = full->idTileCnt.as<uint32_t>();
+    A.start = full->idTileStart.as<uint32_t>(); A.out = nullptr; A.cap = 0;
+    const dim3 grid(gridFor((uint64_t)nTiles * 64, 256));
+    KL(k_indel_count, grid, dim3(256), 0, ctx->stream, A);
+    rc = cubScan(ctx, full->idTileCnt.as<uint32_t>(), full->idTileStart.as<uint32_t>(), nTiles + 1); if (rc) return rc;
+    uint32_t tot = 0, scanFail = 0; unsigned long long h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    { const FetchPiece pc[3] = {{full->idTileStart.as<uint32_t>() + nTiles, &tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1},
+        {full->idStats.p, (uint32_t *)h, 18}}; rc = fetchMany(ctx, pc, 3); if (rc) return rc; }
+    if (scanFail) return scanGaveUp(ctx, "indel alleles");
+    // (the caller sized `out` by ygpu_indels_size: after a ygpu_postfilter that failed half-way the two may differ -- the size is put right, the call fails)
+    if (tot != full->idUsed) { char m[200]; snprintf(m, sizeof m, "ygpu_indels_collect: %u occupied entries, ygpu_indels_size said %u (it now says %u: collect again)", tot,
+        full->idUsed, tot); ctx->err = m; full->idUsed = tot; return YGPU_EINTERNAL; }
+    if (tot) {
+        ENSURE(full->idOut, sizeof(ygpu_indel_entry) * (uint64_t)tot);
+        A.out = full->idOut.as<ygpu_indel_entry>(); A.cap = tot;
+        KL(k_indel_emit, grid, dim3(256), 0, ctx->stream, A);
+        HIPCHK(hipMemcpyAsync(out, full->idOut.p, sizeof(ygpu_indel_entry) * (uint64_t)tot, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    // ... and the table, its statistics and the two words are clean for the next batch
+    HIPCHK(hipMemsetAsync(full->idTable.p, 0, sizeof(ygpu_indel_entry) * full->idCap, ctx->stream));
+    HIPCHK(hipMemsetAsync(full->idStats.p, 0, 128, ctx->stream));
+    HIPCHK(streamSync(ctx));
+    tlsPfFailed = nullptr;
+    full->idUsed = 0;
+    if (stats) { for (int k = 0; k < 5; k++) stats[k] = h[k]; stats[5] = (uint32_t)(h[8] >> 32); }
     return 0;
 }
 // ---- split-read junctions (junction_stage.h; the contract is in ../junction_core.h) --------------------------------------------------------------------------

@@ -4,7 +4,8 @@
 // implementation: -gpus N (shard batches over N devices), -ctx M (contexts per device), -device D, -batch N (reads per device batch),
 // -ocov FILE / -covbin B / -covq Q (read depth of the printed records as bedGraph), -oev FILE / -evbin B / -evq Q / -evclip N (their mismatches, indels and
 // clipped ends per bin), -obp FILE / -bpq Q / -bpw W (split-read breakpoint calls as BEDPE), -opu FILE / -pumin N / -puq Q (the allele pileup: the sites where
-// at least N reads disagree with the reference, with the counts of A C G T N del ins).
+// at least N reads disagree with the reference, with the counts of A C G T N del ins), -oid FILE / -idmin N / -idlen L / -idq Q (indel alleles: position,
+// length and inserted bases of the insertions and deletions at least N printed records carry).
 #include "yaha_host.h"
 #include <cstring>
 #include <cstdlib>
@@ -47,7 +48,13 @@ static void usage(FILE *o)
           "       in index order, written after the last alignment.  Accumulated on the device like the depth, per reference base: 28 bytes of device memory per\n"
           "       reference base per GPU, which is 86.8 GB at 3.1 Gbp; the sites are selected on the device and only they leave it.  When the array does not fit\n"
           "       the run stops before the first batch and says so (use a smaller -ctx).  The host keeps counts only for the records it counts itself, in blocks\n"
-          "       of 4096 reference bases (112 KB each) made when first touched.  Errors in these three options leave with exit code 3 (the other tracks': 2).\n", o);
+          "       of 4096 reference bases (112 KB each) made when first touched.  Errors in these three options leave with exit code 3 (the other tracks': 2).\n"
+          "  indels  : [-oid allelesFile|stdout] [-idmin minRecords (2)] [-idlen minBases (1)] [-idq minMapQ (0)]\n"
+          "       the insertions and deletions of at least -idlen bases that at least -idmin printed records carry, as alleles: tab-separated, no header line --\n"
+          "       chrom, position (1-based: a deletion's first deleted base, an insertion's next reference base), DEL or INS, length, the inserted bases as the\n"
+          "       reference strand shows them (the first 42, then '+'; '*' for a deletion), records -- in index order, written after the last alignment.  Counted\n"
+          "       on the device behind its post-filter in a hash table per context (32 bytes an entry, two entries per base of a batch: 1 GB at the default\n"
+          "       batch), which the host drains whenever a quarter of it is in use.  Errors in these four options leave with exit code 2.\n", o);
 }
 
 static bool parseBool(const char *s, const char *key, bool &out)
@@ -149,6 +156,14 @@ int parseArgs(int argc, char **argv, Args &a)
         else if (is("-pumin")) { if (!parseInt(val(), "-pumin", a.puMinAlt)) return kPileupError; a.havePuMin = true;
             if (a.puMinAlt < 1) { fprintf(stderr, "-pumin must be at least 1 (reads that disagree with the reference).\n\n"); usage(stderr); return kPileupError; } }
         else if (is("-puq")) { if (!parseInt(val(), "-puq", a.puMinQ)) return kPileupError; a.havePuQ = true; }
+        else if (is("-oid")) { const char *v = val(); a.idFileName = (!strcmp(v, "-stdout")) ? "stdout" : v; a.haveId = true;
+            if (a.idFileName.empty()) { fprintf(stderr, "-oid needs a file name.\n\n"); usage(stderr); return 3; } }
+        else if (is("-idmin")) { if (!parseInt(val(), "-idmin", a.idMin)) return 3; a.haveIdMin = true;
+            if (a.idMin < 1) { fprintf(stderr, "-idmin must be at least 1 (records that carry the allele).\n\n"); usage(stderr); return 3; } }
+        else if (is("-idlen")) { if (!parseInt(val(), "-idlen", a.idLen)) return 3; a.haveIdLen = true;
+            if (a.idLen < 1) { fprintf(stderr, "-idlen must be at least 1 (inserted or deleted bases).\n\n"); usage(stderr); return 3; } }
+        else if (is("-idq")) { if (!parseInt(val(), "-idq", a.idMinQ)) return 3; a.haveIdQ = true;
+            if (a.idMinQ < 0 || a.idMinQ > 255) { fprintf(stderr, "-idq must be a mapping quality (0 to 255).\n\n"); usage(stderr); return 3; } }
         else { fprintf(stderr, "%s is not a valid option.\n\n", k); usage(stderr); return 2; }
     }
     a.query = query; a.index = index && !query;
@@ -178,6 +193,14 @@ int parseArgs(int argc, char **argv, Args &a)
         fprintf(stderr, "-opu stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
     if (a.havePu && a.puFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout") || (a.haveBp && a.bpFileName == "stdout"))) {
         fprintf(stderr, "-opu stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
+    // the indel alleles: the same rules, with the older tracks' exit code (2)
+    if (!a.haveId && (a.haveIdMin || a.haveIdLen || a.haveIdQ)) { fprintf(stderr, "-idmin, -idlen and -idq need -oid.\n\n"); usage(stderr); return 3; }
+    if (a.haveId && !query) { fprintf(stderr, "-oid is an output of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return 3; }
+    if (a.haveId && a.idFileName == "stdout" && (!a.haveO || a.ofileName == "stdout")) {
+        fprintf(stderr, "-oid stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
+    if (a.haveId && a.idFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout") || (a.haveBp && a.bpFileName == "stdout")
+        || (a.havePu && a.puFileName == "stdout"))) {
+        fprintf(stderr, "-oid stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
     if ((a.compress || a.uncompress) && !query) {                                                  // Main.c:472-533: -c wants a FASTA genome, -u a .nib2
         if (!a.haveG) { fprintf(stderr, "Genome file specification (-g) is required for index creation.\n\n"); usage(stderr); return 2; }
         size_t dot = a.gfileName.rfind('.'); const std::string ext = dot == std::string::npos ? "" : a.gfileName.substr(dot);
@@ -247,6 +270,7 @@ std::string samHeader(const Args &a, const Genome &g)                   // outpu
     if (a.haveEv) { snprintf(buf, sizeof buf, " -evbin %d -evq %d -evclip %d", a.evBin, a.evMinQ, a.evMinClip); h += " -oev " + a.evFileName + buf; }
     if (a.haveBp) { snprintf(buf, sizeof buf, " -bpq %d -bpw %d", a.bpMinQ, a.bpWindow); h += " -obp " + a.bpFileName + buf; }
     if (a.havePu) { snprintf(buf, sizeof buf, " -pumin %d -puq %d", a.puMinAlt, a.puMinQ); h += " -opu " + a.puFileName + buf; }
+    if (a.haveId) { snprintf(buf, sizeof buf, " -idmin %d -idlen %d -idq %d", a.idMin, a.idLen, a.idMinQ); h += " -oid " + a.idFileName + buf; }
     h += "\n";
     return h;
 }

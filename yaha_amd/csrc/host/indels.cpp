@@ -1,0 +1,111 @@
+// indels.cpp -- the host's side of the indel alleles (-oid): the run's alleles, what the formatter threads count of them, and the writer.  What an event is --
+// a D or I op of at least -idlen bases of a printed record, its slot, the kept bases of an insertion, the two-sequence drop, the MAPQ gate, the walk that never
+// leaves [sqo, eqo] -- and what its key looks like are ../indel_core.h, the source the device stage compiles as well (device/indel_stage.h).
+//
+// The run's alleles are ONE map keyed by the three words, in the file's order.  It is fed by every drain of a context's table during the run, by a last
+// collect per context, and by the formatter threads, which walk the records the device did not count into a list of their own per batch and merge it here
+// under the lock: the map is touched once per batch and per drain, not once per event.
+//
+// The device entry points are WEAK references here, as depth.cpp's are: the host stages are also linked against test doubles that do not have them (the CPU
+// tier), and then -- as when the library refuses to enable the stage -- the host counts every record itself.
+#include "yaha_host.h"
+#include "../indel_core.h"
+#include <algorithm>
+
+extern "C" {
+__attribute__((weak)) int ygpu_indels_enable(ygpu_ctx *ctx, const ygpu_indel_params *p);
+__attribute__((weak)) int ygpu_indels_size(ygpu_ctx *ctx, uint64_t *used);
+__attribute__((weak)) int ygpu_indels_collect(ygpu_ctx *ctx, ygpu_indel_entry *out, uint64_t stats[6]);
+}
+
+namespace yaha {
+
+static inline yindel::Key coreKey(const IndelKey &k) { yindel::Key c; c.w0 = k.w0; c.w1 = k.w1; c.w2 = k.w2; return c; }
+bool IndelKeyLess::operator()(const IndelKey &a, const IndelKey &b) const { return yindel::keyLess(coreKey(a), coreKey(b)); }
+
+bool IndelTrack::init(const Genome &g, int minQ, int minLength, int minRecords, std::string &err)
+{
+    minMapq = (uint32_t)minQ; minLen = (uint32_t)minLength; minCount = (uint32_t)minRecords;
+    seqStart.clear(); seqLength.clear(); for (auto &sq : g.seqs) { seqStart.push_back(sq.start); seqLength.push_back(sq.length); }
+    binBase.assign(seqStart.size() + 1, 0);
+    if (!ydepth::layoutBins(seqLength.data(), (uint32_t)seqLength.size(), 1, binBase.data(), &nSlots)) { err = "-oid: the reference bases do not fit 32 bits"; return false; }
+    return true;
+}
+
+void IndelTrack::add(const OutClump &oc, const Read &r, Local &local) const
+{
+    const ydepth::Layout L{seqStart.data(), seqLength.data(), binBase.data(), (uint32_t)seqStart.size(), 1u, minMapq};
+    std::vector<IndelKey> &keys = local.keys;
+    const int g = yindel::walkClump(L, oc.c, oc.ops, r.fwdCodes.data(), (uint32_t)r.fwdCodes.size(), (oc.status & 0x01) != 0, oc.mapQuality, minLen,
+        [&keys](const yindel::Key &k) { keys.push_back(IndelKey{k.w0, k.w1, k.w2}); });
+    if (g == ydepth::COUNTED) local.records++; else if (g == ydepth::SKIPPED_MAPQ) local.skipped++; else local.dropped++;
+}
+
+void IndelTrack::merge(Local &local)
+{
+    if (local.keys.empty() && !local.records && !local.skipped && !local.dropped) return;
+    std::sort(local.keys.begin(), local.keys.end(), IndelKeyLess());       // (equal keys side by side: one look-up each)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        for (size_t i = 0; i < local.keys.size();) {
+            size_t j = i + 1; while (j < local.keys.size() && yindel::sameKey(coreKey(local.keys[i]), coreKey(local.keys[j]))) j++;
+            alleles[local.keys[i]] += j - i; i = j;
+        }
+        hostEvents += local.keys.size(); hostRecords += local.records; hostSkipped += local.skipped; hostDropped += local.dropped;
+    }
+    local.keys.clear(); local.records = local.skipped = local.dropped = 0;
+}
+
+bool IndelTrack::deviceEntryPoints() { return ygpu_indels_enable != nullptr && ygpu_indels_size != nullptr && ygpu_indels_collect != nullptr; }
+
+int IndelTrack::deviceEnable(ygpu_ctx *ctx, uint64_t capacity) const
+{
+    if (!deviceEntryPoints()) return YGPU_ENODEV;
+    ygpu_indel_params p; memset(&p, 0, sizeof p);
+    p.min_mapq = minMapq; p.min_length = minLen; p.n_seqs = (uint32_t)seqStart.size(); p.seq_start = seqStart.data(); p.seq_length = seqLength.data(); p.capacity = capacity;
+    return ygpu_indels_enable(ctx, &p);
+}
+
+int IndelTrack::deviceSize(ygpu_ctx *ctx, uint64_t *used) const { return deviceEntryPoints() ? ygpu_indels_size(ctx, used) : YGPU_ENODEV; }
+
+int IndelTrack::deviceDrain(ygpu_ctx *ctx, bool duringRun, std::string &err)
+{
+    if (!deviceEntryPoints()) return YGPU_ENODEV;
+    uint64_t n = 0, st[6] = {0, 0, 0, 0, 0, 0};
+    int rc = ygpu_indels_size(ctx, &n);
+    std::vector<ygpu_indel_entry> got((size_t)n);
+    if (rc == 0) rc = ygpu_indels_collect(ctx, got.data(), st);
+    if (rc != 0) { err = ygpu_last_error(ctx); return rc; }
+    std::lock_guard<std::mutex> lk(mu);
+    for (const ygpu_indel_entry &e : got) alleles[IndelKey{e.w0, e.w1, e.w2}] += e.count;
+    devRecords += st[0]; devSkipped += st[1]; devDropped += st[2]; devEvents += st[3]; devHandedBack += st[4]; devLost += st[5];
+    if (duringRun) drains++;
+    return 0;
+}
+
+// One line per allele at least minCount records carry, in the map's order: name, position (1-based within the sequence: a deletion's first deleted base, an
+// insertion's slot), DEL / INS, length, the kept bases of an insertion ('+' behind them when it is longer) or '*', the count.
+bool IndelTrack::write(const char *path, const Genome &g, std::string &err)
+{
+    FILE *f = !strcmp(path, "stdout") ? stdout : fopen(path, "w");
+    if (!f) { err = std::string("Failure to open the indel allele file: ") + path + "."; return false; }
+    bool ok = true; size_t s = 0; nLines = 0; char bases[yindel::KEPT + 2];
+    for (auto it = alleles.begin(); it != alleles.end() && ok; ++it) {
+        if (it->second < minCount) continue;
+        const yindel::Key k = coreKey(it->first); const uint32_t slot = yindel::slotOfKey(k);
+        if (slot >= nSlots) continue;
+        while (s + 1 < g.seqs.size() && slot >= binBase[s + 1]) s++;
+        const bool ins = yindel::typeOfKey(k) == (uint32_t)yindel::INS; const uint32_t kept = yindel::keptOfKey(k); uint32_t n = 0;
+        for (; n < kept; n++) bases[n] = "ACGTN"[std::min(yindel::baseOfKey(k, n), 4u)];
+        if (ins && yindel::lenOfKey(k) > (uint32_t)yindel::KEPT) bases[n++] = '+';
+        if (!ins) bases[n++] = '*';
+        bases[n] = 0;
+        ok = fprintf(f, "%s\t%u\t%s\t%u\t%s\t%llu\n", g.seqs[s].name.c_str(), slot - binBase[s] + 1, ins ? "INS" : "DEL", yindel::lenOfKey(k), bases,
+            (unsigned long long)it->second) > 0;
+        nLines++;
+    }
+    if (f == stdout) ok = fflush(f) == 0 && ok; else ok = fclose(f) == 0 && ok;
+    if (!ok) err = std::string("Failure writing the indel allele file: ") + path + ".";
+    return ok;
+}
+}  // namespace yaha

@@ -5,6 +5,7 @@
 // output is re-ordered by batch ticket, so the text equals a `-t 1` run of the reference.
 #include "yaha_host.h"
 #include "../oqc_core.h"
+#include "../indel_core.h"
 #include <cstring>
 #include <cstdlib>
 #include <thread>
@@ -29,6 +30,8 @@ struct yaha_session {
     std::vector<BinnedTrack *> tracks;                               // -ocov, -oev, -opu (the command line): the formatters add the records the device did not count
     // -obp: the formatters make the junctions of the reads the device did not (junctions.cpp) into the batch's own list; their counts of the batch
     const JunctionTrack *junctions = nullptr; std::vector<ygpu_junction> *jnOut = nullptr; uint64_t jnReads = 0, jnSkipped = 0;
+    // -oid: the formatters walk the records the device did not count (indels.cpp) into a list of their own, merged into the run's alleles once per batch
+    const IndelTrack *indels = nullptr; IndelTrack::Local idLocal;
 };
 
 namespace yaha {
@@ -134,12 +137,14 @@ static void hostJunctions(yaha_session *s, uint32_t i, const OutClump *recs, uin
     s->jnSkipped += skipped;
 }
 // What of a batch was counted on the device, as a bit mask: bit t = the session's binned track t; the batch's junctions were made there as well
-enum : unsigned { kJunctionsOnDevice = 1u << 31 };
+// (and its indel alleles were counted there)
+enum : unsigned { kJunctionsOnDevice = 1u << 31, kIndelsOnDevice = 1u << 30 };
 // one record of read i: its text, and its share of every binned track the device did not count it for
 static inline void emitRecord(yaha_session *s, uint32_t i, const OutClump &o, int primaryCount, Text &text, unsigned onDevice = 0)
 {
     printClump(s->args, s->genome, s->reads[i], o, primaryCount, text);
     for (size_t t = 0; t < s->tracks.size(); t++) if (!(onDevice >> t & 1u)) s->tracks[t]->add(o, s->reads[i]);
+    if (s->indels && !(onDevice & kIndelsOnDevice)) s->indels->add(o, s->reads[i], s->idLocal);
 }
 static void formatRange(yaha_session *s, const ygpu_result_batch *r, uint32_t i0, uint32_t i1, Text &text, std::vector<OutClump> &oc)
 {
@@ -261,6 +266,15 @@ int runQueries(Args &a, FILE *log)
     // -obp: the run's junctions (junctions.cpp); a batch's are made on the device behind its post-filter and travel with it
     std::unique_ptr<JunctionTrack> junctions;
     if (A.haveBp) { junctions.reset(new JunctionTrack); junctions->init(S->genome, A.bpMinQ, A.bpWindow); }
+    // -oid: the run's indel alleles (indels.cpp); the device counts them in a table per context, drained during the run and at its end.  The table has two
+    // entries per base of the largest batch the splitter cuts (indel_core.h tableCapacity), as far as that is known before the reads are: -batch N gives a read
+    // count, and N reads of the greatest length would ask for more than a batch ever holds -- the table then stops at that of the default batch, and a drain
+    // before a batch that could pass half of it keeps the load where the rule wants it.
+    std::unique_ptr<IndelTrack> indels;
+    if (A.haveId) { indels.reset(new IndelTrack); if (!indels->init(S->genome, A.idMinQ, A.idLen, A.idMin, S->err)) { fprintf(log, "%s\n", S->err.c_str()); return 1; } }
+    const uint64_t idCapacity = yindel::tableCapacity(A.batchReads > 0 ? std::min<uint64_t>((uint64_t)A.batchReads * (uint64_t)std::max(1, A.maxQueryLength), (uint64_t)16 << 20)
+                                                                       : (uint64_t)16 << 20);
+    std::vector<char> idEnabled((size_t)ngpu, 0);
     setvbuf(out, nullptr, _IONBF, 0);                                       // whole batches are written with one call each
     if (fputs(S->header.c_str(), out) < 0) { fprintf(log, "Failure writing the output file.\n"); return 1; }
     ygpu_params P; paramsFromArgs(A, P);
@@ -368,6 +382,8 @@ int runQueries(Args &a, FILE *log)
     for (auto &T : tracks) T.onDevice = deviceFilter && T.track->deviceEntryPoints() && getenv(T.hostSwitch) == nullptr;
     // the junctions on the device: per context and per batch, nothing shared (YAHA_HOST_JUNCTIONS: the formatters make them all)
     const bool junctionsDevice = junctions && deviceFilter && JunctionTrack::deviceEntryPoints() && getenv("YAHA_HOST_JUNCTIONS") == nullptr;
+    // the indel alleles on the device: a table per context (YAHA_HOST_INDELS: the formatters count them all)
+    const bool indelsDevice = indels && deviceFilter && IndelTrack::deviceEntryPoints() && getenv("YAHA_HOST_INDELS") == nullptr;
     std::vector<std::atomic<uint64_t>> devReads(nDev); for (auto &x : devReads) x = 0;       // reads each device took (the stats line: do all devices pull their weight?)
     // where a context thread's time goes, batches after a context's first (the stats line; microseconds): upload, run, waiting for the filter thread, snapshot; and the filter
     // thread's post-filter + collect
@@ -404,6 +420,12 @@ int runQueries(Args &a, FILE *log)
             else if (rcT == 0) ctxOnDevice |= 1u << t;
         }
         if (rc0 == 0 && junctionsDevice && junctions->deviceEnable(ctx[d]) == 0) ctxOnDevice |= kJunctionsOnDevice;      // (refused: the formatters make this context's)
+        // (no room for the indel table: the run stops here, as for the arrays; refused otherwise: the formatters count this context's)
+        if (rc0 == 0 && indelsDevice) {
+            const int rcI = indels->deviceEnable(ctx[d], idCapacity);
+            if (rcI == YGPU_ENOMEM) { char m[640]; snprintf(m, sizeof m, "-oid: %s", ygpu_last_error(ctx[d])); fail(m); }
+            else if (rcI == 0) { ctxOnDevice |= kIndelsOnDevice; idEnabled[d] = 1; }
+        }
         if (rc0 != 0) { char m[512];
             snprintf(m, sizeof m, "ygpu_init(device %d) failed: %d %s", dev, rc0, ctx[d] ? ygpu_last_error(ctx[d]) : (d == leadCtx ? "" : "(the device's first context failed)"));
             fail(m); }
@@ -424,8 +446,17 @@ int runQueries(Args &a, FILE *log)
         const bool overlapFilter = deviceFilter && getenv("YAHA_SERIAL_FILTER") == nullptr;
         // post-filter (of the snapshot, or of the context's last run) and its results into the batch's own buffers
         auto collectFiltered = [&](BatchP &fb, ygpu_result_batch &res) -> int {
-            uint64_t nc = 0, no = 0;
-            int rc = ygpu_postfilter(ctx[d]); if (rc == 0) rc = ygpu_filtered_size(ctx[d], &nc, &no); if (rc != 0) return rc;
+            uint64_t nc = 0, no = 0; int rc = 0;
+            // the indel table: drained BEFORE a batch that could take it past one half (a batch has at most one event per two bases) ...
+            const bool idOn = (fb->onDevice & kIndelsOnDevice) != 0; std::string ierr;
+            if (idOn) { uint64_t used = 0; rc = indels->deviceSize(ctx[d], &used);
+                if (rc == 0 && used && used + fb->codes.size() / 2 > idCapacity / 2) rc = indels->deviceDrain(ctx[d], true, ierr);
+                if (rc != 0) return rc; }
+            rc = ygpu_postfilter(ctx[d]); if (rc == 0) rc = ygpu_filtered_size(ctx[d], &nc, &no); if (rc != 0) return rc;
+            // ... and whenever more than a quarter of it is in use after one
+            if (idOn) { uint64_t used = 0; rc = indels->deviceSize(ctx[d], &used);
+                if (rc == 0 && used > idCapacity / 4) rc = indels->deviceDrain(ctx[d], true, ierr);
+                if (rc != 0) return rc; }
             // (the batch's junctions: few, and on their way while the clumps are sized)
             if (fb->onDevice & kJunctionsOnDevice) { rc = junctions->deviceCollect(ctx[d], fb->jnDev, fb->jnDevStats); if (rc != 0) return rc; }
             if (!fb->clumpStart.ensure(4 * (fb->nReads + 1)) || !fb->clumps.ensure(sizeof(ygpu_out_clump) * nc) || !fb->ops.ensure(4 * no)) return YGPU_ENOMEM;
@@ -549,7 +580,7 @@ int runQueries(Args &a, FILE *log)
         yaha_session local; local.args = A; local.genome.bases = S->genome.bases; local.genome.nBaseBytes = S->genome.nBaseBytes; local.genome.seqs = S->genome.seqs;
             local.genome.maxROff = S->genome.maxROff;
         for (auto &T : tracks) local.tracks.push_back(T.track.get());
-        local.junctions = junctions.get();
+        local.junctions = junctions.get(); local.indels = indels.get();
         BatchP b;
         while (fmtQ.pop(b)) {
             const double t0 = now(); b->text.clear();
@@ -568,6 +599,7 @@ int runQueries(Args &a, FILE *log)
                 local.reads.swap(b->reads); formatBatch(&local, &res, b->text, 1); local.reads.swap(b->reads);
             }
             b->jnHostReads = local.jnReads; b->jnHostSkipped = local.jnSkipped;
+            if (indels) indels->merge(local.idLocal);
             b->tFmt = now() - t0;
             outQ.push(std::move(b));
         }
@@ -627,6 +659,18 @@ int runQueries(Args &a, FILE *log)
         if (fflush(out) != 0) rcAll = 1;
         if (rcAll == 0 && !junctions->write(A.bpFileName.c_str(), S->genome, jerr)) { fprintf(log, "%s\n", jerr.c_str()); rcAll = 1; }
     }
+    // the indel alleles: what every context's table still holds, then the file, after the breakpoint calls
+    if (indels && !stop && rcAll == 0) {
+        std::string ierr;
+        for (int d = 0; d < ngpu && rcAll == 0; d++) if (idEnabled[d] && ctx[d]) {
+            const int rcI = indels->deviceDrain(ctx[d], false, ierr);
+            if (rcI != 0) { fprintf(log, "-oid: collecting the indel table of context %d failed (%d): %s\n", d, rcI, ierr.c_str()); rcAll = 1; }
+        }
+        if (indels->devLost) { fprintf(log, "-oid: %llu indel events found no entry in a device table -- the file would be incomplete.\n", (unsigned long long)indels->devLost);
+            rcAll = 1; }
+        if (fflush(out) != 0) rcAll = 1;
+        if (rcAll == 0 && !indels->write(A.idFileName.c_str(), S->genome, ierr)) { fprintf(log, "%s\n", ierr.c_str()); rcAll = 1; }
+    }
     const bool fastExit = getenv("YAHA_FAST_EXIT") != nullptr;
     if (!fastExit) for (int d = ngpu - 1; d >= 0; d--) if (ctx[d]) ygpu_destroy(ctx[d]);     // clones before their parents
     // (the batches -- a million small strings, the page-locked buffers -- go with the process as well: freeing them one by one was 0.3 s)
@@ -639,7 +683,7 @@ int runQueries(Args &a, FILE *log)
         std::string per = "[";
         for (int k = 0; k < nDev; k++) { char t[32]; snprintf(t, sizeof t, "%s%llu", k ? ", " : "", (unsigned long long)devReads[k].load()); per += t; }
         per += "]";
-        char dstat[768] = "";
+        char dstat[1280] = "";
         for (auto &T : tracks) { const size_t at = strlen(dstat); const BinnedTrack &t = *T.track;
             snprintf(dstat + at, sizeof dstat - at, T.statsFmt, (unsigned long long)t.nBins, (unsigned long long)t.devRecords, (unsigned long long)t.hostRecords,
                 (unsigned long long)t.sum());
@@ -647,6 +691,11 @@ int runQueries(Args &a, FILE *log)
         if (junctions) { const size_t at = strlen(dstat);
             snprintf(dstat + at, sizeof dstat - at, ", \"bp_device_reads\": %llu, \"bp_host_reads\": %llu, \"bp_junctions\": %llu, \"bp_clusters\": %llu",
                 (unsigned long long)junctions->devReads, (unsigned long long)junctions->hostReads, (unsigned long long)nJunctions, (unsigned long long)junctions->nClusters); }
+        if (indels) { const size_t at = strlen(dstat);
+            snprintf(dstat + at, sizeof dstat - at, ", \"indel_device_records\": %llu, \"indel_host_records\": %llu, \"indel_events\": %llu, \"indel_alleles\": %llu, "
+                "\"indel_lines\": %llu, \"indel_drains\": %llu, \"indel_lost\": %llu", (unsigned long long)indels->devRecords, (unsigned long long)indels->hostRecords,
+                (unsigned long long)(indels->devEvents + indels->hostEvents), (unsigned long long)indels->alleles.size(), (unsigned long long)indels->nLines,
+                (unsigned long long)indels->drains, (unsigned long long)indels->devLost); }
         fprintf(stderr, "[yaha] stats {\"reads\": %llu, \"contexts_up_ms\": %.1f, \"first_batch_written_ms\": %.1f, \"last_batch_written_ms\": %.1f, \"total_ms\": %.1f, "
             "\"steady_reads_per_s\": %.0f, \"cpus\": %d, \"formatters\": %d, \"parsers\": %d, \"gpus\": %d, \"ctx_per_gpu\": %d, \"ctx_left_out\": %d, "
             "\"reads_per_device\": %s, \"context_thread_ms_per_batch\": {\"wait_for_a_batch\": %.2f, \"upload\": %.2f, \"run\": %.2f, \"wait_for_filter_thread\": %.2f, "
@@ -723,6 +772,14 @@ int yaha_session_pileup_params(yaha_session *s, ygpu_pileup_params *p)
 {
     if (!s || !p) return YGPU_EINVAL;
     p->min_mapq = (uint32_t)s->args.puMinQ; p->n_seqs = (uint32_t)s->seqStart.size(); p->seq_start = s->seqStart.data(); p->seq_length = s->seqLen.data();
+    return 0;
+}
+int yaha_session_indel_params(yaha_session *s, ygpu_indel_params *p)
+{
+    if (!s || !p) return YGPU_EINVAL;
+    memset(p, 0, sizeof *p);
+    p->min_mapq = (uint32_t)s->args.idMinQ; p->min_length = (uint32_t)s->args.idLen; p->n_seqs = (uint32_t)s->seqStart.size(); p->seq_start = s->seqStart.data();
+        p->seq_length = s->seqLen.data();
     return 0;
 }
 int yaha_session_junction_params(yaha_session *s, ygpu_junction_params *p)

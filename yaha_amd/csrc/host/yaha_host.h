@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <map>
+#include <mutex>
 #include <vector>
 #include <memory>
 #include <cstdlib>
@@ -80,6 +82,8 @@ struct Args {
     bool haveBp = false, haveBpQ = false, haveBpW = false; std::string bpFileName; int bpMinQ = 0, bpWindow = 10;
     // allele pileup: -opu FILE (the sites where at least -pumin reads disagree with the reference, with the counts of A C G T N del ins), -puq Q
     bool havePu = false, havePuMin = false, havePuQ = false; std::string puFileName; int puMinAlt = 2, puMinQ = 0;
+    // indel alleles: -oid FILE (one line per insertion / deletion allele that at least -idmin printed records carry), -idlen L (shortest op counted), -idq Q
+    bool haveId = false, haveIdMin = false, haveIdLen = false, haveIdQ = false; std::string idFileName; int idMin = 2, idLen = 1, idMinQ = 0;
     bool query = false, index = true, compress = false, uncompress = false;   // -c / -u: .fa -> .nib2 / .nib2 -> .fasta only (Main.c:284-293, non-user builds of the reference)
 };
 void postProcessArgs(Args &a, bool query);                                  // AlignArgs.c:108-169
@@ -248,6 +252,30 @@ struct JunctionTrack {
     int  deviceEnable(ygpu_ctx *ctx) const;                               // YGPU_ENODEV without the entry points
     int  deviceCollect(ygpu_ctx *ctx, std::vector<ygpu_junction> &out, uint64_t stats[4]) const;      // the junctions of the context's last ygpu_postfilter
     bool write(const char *path, const Genome &g, std::string &err);      // clusters and writes; path "stdout" = standard output
+};
+
+// ---- indel alleles (-oid; indels.cpp, ../indel_core.h) --------------------------------------------------------------------------------------------------------
+// The run's alleles -- (slot, type, length, inserted bases) -> records that carry it -- and their writer.  The device counts them in a hash table per context
+// behind its post-filter (ygpu_indels_*, looked up weakly as the tracks' entry points are): the pipeline drains a context's table whenever more than a quarter
+// of it is in use, and once more at the end.  The formatter threads count what the device did not -- runs whose post-filter stays on the host, the reads it
+// hands back unfiltered, builds without the entry points -- with the same walk (indel_core.h) into a list of their own per batch, merged here under a lock.
+struct IndelKey { uint64_t w0, w1, w2; };
+struct IndelKeyLess { bool operator()(const IndelKey &a, const IndelKey &b) const; };      // the order of the file (indel_core.h keyLess)
+struct IndelTrack {
+    std::vector<uint32_t> seqStart, seqLength, binBase; uint64_t nSlots = 0; uint32_t minMapq = 0, minLen = 1, minCount = 2;
+    std::mutex mu; std::map<IndelKey, uint64_t, IndelKeyLess> alleles;
+    uint64_t hostRecords = 0, hostSkipped = 0, hostDropped = 0, hostEvents = 0;           // (under mu, by merge)
+    uint64_t devRecords = 0, devSkipped = 0, devDropped = 0, devEvents = 0, devHandedBack = 0, devLost = 0, drains = 0, nLines = 0;
+    // what a formatter thread gathers of one batch before it merges: the events' keys and what became of the records it walked
+    struct Local { std::vector<IndelKey> keys; uint64_t records = 0, skipped = 0, dropped = 0; };
+    bool init(const Genome &g, int minQ, int minLength, int minRecords, std::string &err);
+    void add(const OutClump &oc, const Read &r, Local &local) const;      // one record printClump was called for
+    void merge(Local &local);                                             // ... and the batch's share into the run's alleles; clears local
+    static bool deviceEntryPoints();                                      // does this build have ygpu_indels_*?
+    int  deviceEnable(ygpu_ctx *ctx, uint64_t capacity) const;            // YGPU_ENODEV without the entry points
+    int  deviceSize(ygpu_ctx *ctx, uint64_t *used) const;
+    int  deviceDrain(ygpu_ctx *ctx, bool duringRun, std::string &err);    // collects and clears the context's table into the run's alleles
+    bool write(const char *path, const Genome &g, std::string &err);      // applies minCount; path "stdout" = standard output
 };
 }  // namespace yaha
 namespace yoqc { struct Params; }
