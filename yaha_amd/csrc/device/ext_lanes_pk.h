@@ -16,8 +16,9 @@
 // V(0, j) = -(GO + (j - 10) GE) in the problem's first iteration.  A problem of i rows takes i + 1 iterations; row t's maximum is known after iteration t + 1.
 //
 // Decisions are the sign bits of saturating differences (no compares, no SGPR pairs): bit 15 / 31 of  dT = E - G (set: E does NOT win), dU = F - max(G, E),
-// dE = (PE - GE) - (PV - GOE) (set: the E run does NOT continue), dF likewise.  v_perm_b32 gathers the sign BYTES of two registers (both halves), v_bfi shifts
-// them into bit planes: one trace record (16 bytes) per iteration and lane,
+// dE = (PE - GE) - (PV - GOE) (set: the E run does NOT continue), dF likewise.  v_perm_b32 returns the signs of two registers' four halves as four whole bytes
+// (0x00 / 0xFF: its sign-extension selectors 8..11, see pkSignBytes), one v_bfi under a constant mask puts pair k's bit of all four bytes in place
+// (YD_ROWS_SIGNSEL; before: the halves' high bytes, shifted down the planes a bit per pair): one trace record (16 bytes) per iteration and lane,
 //     dword 0 (AB2): pairs 8..10: bits 5..7 of the A bytes, bits 2..4 of the B bytes
 //     dword 1 (M):   mismatch bits, pair k at bit 10 - k (low half) and 26 - k (high half)
 //     dword 2 (A):   byte 0 = notT low half, byte 1 = notT high half, byte 2 = notU low, byte 3 = notU high;  bit k of a byte = pair k (k = 0..7)
@@ -51,6 +52,12 @@ __device__ __forceinline__ uint32_t pkSignMask(uint32_t a) { return pkU(pkS(a) >
 // 16-bit compares and two selects, which cost twice as much here (v_cmp writes an SGPR pair)
 __device__ __forceinline__ uint32_t pkSignMaskAsm(uint32_t a, uint32_t c15) { uint32_t d; asm("v_pk_ashrrev_i16 %0, %1, %2" : "=v"(d) : "v"(c15), "v"(a)); return d; }
 __device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) { return (a & mask) | (b & ~mask); }                      // v_bfi_b32
+// the signs of the four 16-bit halves of (hi, lo) as whole bytes: byte 0 = lo's low half, 1 = lo's high half, 2 = hi's low half, 3 = hi's high half, each 0x00 or
+// 0xFF.  v_perm_b32 D = perm(S0, S1, sel): a selector byte of 0..3 picks that byte of S1, 4..7 of S0; 8, 9, 10, 11 return the SIGN of byte 1 / 3 of S1 and of
+// byte 1 / 3 of S0 replicated over the byte (bit 15 / 31 of S1, bit 15 / 31 of S0); 12 returns 0x00, 13 and above 0xFF.
+__device__ __forceinline__ uint32_t pkSignBytes(uint32_t hi, uint32_t lo) { return __builtin_amdgcn_perm(hi, lo, 0x0B0A0908u); }
+// v_bfi_b32 with the mask in a SCALAR register (YD_ROWS_SIGNSEL=2: an opaque mask written as the expression above is not matched to v_bfi any more)
+__device__ __forceinline__ uint32_t bfiS(uint32_t mask, uint32_t a, uint32_t b) { uint32_t d; asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "s"(mask), "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ uint32_t pk2(int v) { return ((uint32_t)v & 0xFFFFu) * 0x10001u; }
 
 // YD_ROWS_LDSWIN (round 5): the two nibble streams of a lane -- query codes, reference bases -- come from HBM in ALIGNED 16-BYTE PIECES (one request per lane and 32
@@ -82,6 +89,17 @@ __device__ unsigned long long gRowsProf[8];      // passes, passes that wrote re
 #define YD_ROWS_EXIT(c) UNI_B(c)
 #else
 #define YD_ROWS_EXIT(c) (c)
+#endif
+// YD_ROWS_SIGNSEL=1: the decision bits reach the record as SIGN-EXTENSION BYTES.  v_perm_b32's selectors 8..11 return 0x00 or 0xFF, eight copies of the sign of a
+// 16-bit half, so pair k's bit of all four bytes of a plane goes in place with one v_bfi under the constant mask 0x01010101 << k: the accumulator is not
+// shifted, dword 0 needs one accumulator instead of two and a merge, and nothing is zeroed per pass (every bit that can be set is overwritten in every row).
+// 0: the high BYTES of the halves (selectors 1, 3, 5, 7; the sign at bit 7), shifted down a bit per pair.  The records are the same bit for bit.
+#ifndef YD_ROWS_SIGNSEL
+#define YD_ROWS_SIGNSEL 1
+#endif
+// YD_ROWS_M_LSHL_OR=1: the mismatch plane's accM = (accM << 1) | mm kept to one v_lshl_or_b32 a pair (the compiler's own pairing costs 1.5)
+#ifndef YD_ROWS_M_LSHL_OR
+#define YD_ROWS_M_LSHL_OR YD_ROWS_SIGNSEL
 #endif
 #ifndef YD_ROWS_WAVES
 #define YD_ROWS_WAVES 3                        // waves per SIMD of k_ext_rows_pk (a build switch for experiments: make variant VARIANT_FLAGS=-DYD_ROWS_WAVES=2)
@@ -177,6 +195,19 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
     };
     auto nextFlush = [&]() { flush++; if (flush % YD_CHUNK_FLUSHES == 0u) takeChunk(); };     // wave-uniform
     bool firstFill = true;
+#if YD_ROWS_SIGNSEL
+    uint32_t accA = 0, accB = 0, accAB2 = 0;                                 // the record's decision planes (bits 0 and 1 of accAB2's bytes are never written: they stay 0)
+#if YD_ROWS_SIGNSEL == 2
+    uint32_t bitMask[8];                                                     // 0x01010101 << k, pinned in scalar registers for the whole kernel
+#pragma unroll
+    for (int k = 0; k < 8; k++) { bitMask[k] = 0x01010101u << k; asm volatile("" : "+s"(bitMask[k])); }
+#define YD_ROWS_INS(k, s, acc) bfiS(bitMask[k], s, acc)
+#else
+    // (the mask is a literal: one s_mov_b32 a pair inside the row code, on the scalar unit, which this kernel leaves idle.  Pinned in scalar registers -- 2 -- the
+    // eight masks push seven more of the kernel's wave-uniform values into spill lanes, and every v_readlane that brings one back is a vector instruction.)
+#define YD_ROWS_INS(k, s, acc) bfi(0x01010101u << (k), s, acc)
+#endif
+#endif
     for (;;) {
         // (Round 6, measured and dropped: every wave-uniform condition of this loop through UNI_B and every uniform counter through uni().  Left to itself the compiler
         // takes the loop's exits for lane-dependent -- an EXEC-masked loop, the uniform state in vector registers, twenty moves and thirty mask instructions a pass --
@@ -416,7 +447,11 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
         uint32_t PVCol = (PV[YD_NP - 1] << 16) | LWgLo;                      // (Vg) low: nothing left of column 0; high: V(i-1, 10)
         uint32_t PE = (carryE << 16) | LWlo;                                 //                                       E(i-1, 10)
         uint32_t rowMax = LWp, dV = PV[0];
+#if YD_ROWS_SIGNSEL
+        uint32_t accM = 0;                                                   // (accA, accB, accAB2 live across the passes: every bit that can be set is rewritten in every row)
+#else
         uint32_t accA = 0, accB = 0, accA2 = 0, accB2 = 0, accM = 0;
+#endif
 #pragma unroll
         for (int k = 0; k < YD_NP; k++) {
             const uint32_t mm = pkMinU(rc[k] ^ qcPv, ONEv);                   // 0 = match, 1 = mismatch, per half
@@ -434,11 +469,22 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
             const uint32_t dF = pkSub(CF, NF);
             const uint32_t dU = pkSub(F, V);
             V = pkMax(V, F);
+#if YD_ROWS_SIGNSEL
+            // signs of both halves as whole bytes (0x00 / 0xFF) -> pair k's bit of every byte of the plane, in place: one constant-mask v_bfi, no shift
+            const uint32_t S1 = pkSignBytes(dU, dT), S2 = pkSignBytes(dF, dE);
+            if (k < 8) { accA = YD_ROWS_INS(k, S1, accA); accB = YD_ROWS_INS(k, S2, accB); asm volatile("" : "+v"(accA), "+v"(accB)); }
+            // dword 0: pair k's A bits are bit k - 3 of every byte (5..7), its B bits bit k - 6 (2..4).  (Opaque between the two: merged, they become three ands and a v_or3.)
+            else { accAB2 = YD_ROWS_INS(k - 3, S1, accAB2); asm volatile("" : "+v"(accAB2)); accAB2 = YD_ROWS_INS(k - 6, S2, accAB2); asm volatile("" : "+v"(accAB2)); }
+#else
             // sign bytes of both halves -> bit planes
             const uint32_t S1 = __builtin_amdgcn_perm(dU, dT, 0x07050301u), S2 = __builtin_amdgcn_perm(dF, dE, 0x07050301u);
             if (k < 8) { accA = bfi(0x80808080u, S1, accA >> 1); accB = bfi(0x80808080u, S2, accB >> 1); asm volatile("" : "+v"(accA), "+v"(accB)); }
             else { accA2 = bfi(0x80808080u, S1, accA2 >> 1); accB2 = bfi(0x80808080u, S2, accB2 >> 1); asm volatile("" : "+v"(accA2), "+v"(accB2)); }
+#endif
             accM = (accM << 1) | mm;
+#if YD_ROWS_M_LSHL_OR
+            asm volatile("" : "+v"(accM));                                    // (opaque: one v_lshl_or_b32 a pair; left alone, two pairs become lshl, lshl, v_or3)
+#endif
             // row-major first maximum over the real cells, per half.  Low half: the columns left of the matrix (one of them is the boundary column, with a
             // real-sized value) have a reference code that is negative as a score (0x800F), the cells of the matrix one that is above every score (0x7FF0 | nibble):
             // one minimum.  High half of pair 10: the column that does not exist.
@@ -451,7 +497,11 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
         }
         carryE = PE;
         { const int slot = wslot * 4;                                        // this iteration's record goes to the lane's LDS block (the same slot in every lane)
+#if YD_ROWS_SIGNSEL
+          myBlk[slot] = accAB2; myBlk[slot + 1] = accM; myBlk[slot + 2] = accA; myBlk[slot + 3] = accB; }
+#else
           myBlk[slot] = accA2 | (accB2 >> 3); myBlk[slot + 1] = accM; myBlk[slot + 2] = accA; myBlk[slot + 3] = accB; }
+#endif
         // row i - 1 is complete now: its maximum (columns 0..10 from the previous iteration, 11..20 from this one; the first one in column order), X-drop test
         // The scan is row-major with a strict '>': row i-1's columns 11..20 (this iteration's high halves) come after its columns 0..10 (seen one iteration ago),
         // and before row i's columns 0..10 (this iteration's low halves, counted unless row i-1 ends the problem).  The strip of the iteration that set the
