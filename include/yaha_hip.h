@@ -475,6 +475,21 @@ int  yaha_session_pileup_params(yaha_session *s, ygpu_pileup_params *p);
 int  yaha_session_indel_params(yaha_session *s, ygpu_indel_params *p);
 /* The same for ygpu_junctions_enable: -bpq (default 0) and the sequence table (pointers of their own into the session). */
 int  yaha_session_junction_params(yaha_session *s, ygpu_junction_params *p);
+/* ---- BGZF compression on the device (-obh / -obs: BAM output; device/bgzf.hip, csrc/bgzf_core.h) ---------------------------------------------------------
+ * A primitive of its own: a handle has its own stream, device buffers and page-locked staging for inputs of up to max_in_bytes; it touches no ygpu_ctx.
+ * Handles are independent: two threads with two handles may compress at the same time; one handle serves one thread at a time.
+ * compress cuts in[0 .. n_in) into payloads of 65 280 bytes (the last one shorter), deflates every payload into one BGZF block on the device (one workgroup
+ * a block, fixed Huffman codes, the stored form wherever that is not larger; CRC-32 on the device as well) and writes the blocks one after the other, in
+ * order, to out; *n_out = their bytes.  n_in == 0 gives *n_out == 0: no end-of-file block is added, the writer of a file owns that.  out_cap must be at least
+ * bound(n_in) = ceil(n_in / 65280) * 65536.  An input over max_in_bytes or a smaller out_cap is YGPU_EINVAL, and the handle stays usable.  The same input
+ * gives the same bytes every time. */
+typedef struct ygpu_bgzf ygpu_bgzf;
+int  ygpu_bgzf_open(int device, uint64_t max_in_bytes, ygpu_bgzf **h);
+uint64_t ygpu_bgzf_bound(uint64_t n_in);
+int  ygpu_bgzf_compress(ygpu_bgzf *h, const void *in, uint64_t n_in, void *out, uint64_t out_cap, uint64_t *n_out);
+const char *ygpu_bgzf_last_error(ygpu_bgzf *h);
+int  ygpu_bgzf_close(ygpu_bgzf *h);
+
 /* `yaha -g genome.fa [-L k] [-S s] [-H h]`: writes genome.nib2 and genome.X<LL>_<SS>_<HHHHH>S (Main.c:554-628). */
 int  yaha_build_index(int argc, const char *const *argv);
 /* The complete command-line program (index creation or query alignment on the GPU). */

@@ -47,6 +47,11 @@ int  ygpu_indels_collect(ygpu_ctx *, ygpu_indel_entry *, uint64_t *) { return YG
 int  ygpu_junctions_enable(ygpu_ctx *, const ygpu_junction_params *) { return YGPU_ENODEV; }
 int  ygpu_junctions_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
 int  ygpu_junctions_collect(ygpu_ctx *, ygpu_junction *, uint64_t *) { return YGPU_ENODEV; }
+int  ygpu_bgzf_open(int, uint64_t, ygpu_bgzf **h) { if (h) *h = nullptr; return YGPU_ENODEV; }      // (host/bam.cpp then compresses with the host's encoder)
+uint64_t ygpu_bgzf_bound(uint64_t n) { return (n + 65279) / 65280 * 65536; }
+int  ygpu_bgzf_compress(ygpu_bgzf *, const void *, uint64_t, void *, uint64_t, uint64_t *) { return YGPU_ENODEV; }
+const char *ygpu_bgzf_last_error(ygpu_bgzf *) { return "sanitizer build: no device code"; }
+int  ygpu_bgzf_close(ygpu_bgzf *) { return 0; }
 void *ygpu_host_alloc(size_t) { return nullptr; }
 void ygpu_host_free(void *) {}
 int  ygpu_submit(ygpu_ctx *, const ygpu_read_batch *, ygpu_ticket *) { return YGPU_ENODEV; }

@@ -166,6 +166,7 @@ EXPORTS = (
     "yaha_session_pileup_params",
     "ygpu_indels_enable", "ygpu_indels_size", "ygpu_indels_collect", "yaha_session_indel_params",
     "ygpu_junctions_enable", "ygpu_junctions_size", "ygpu_junctions_collect", "yaha_session_junction_params",
+    "ygpu_bgzf_open", "ygpu_bgzf_bound", "ygpu_bgzf_compress", "ygpu_bgzf_last_error", "ygpu_bgzf_close",
     "ygpu_submit", "ygpu_poll", "ygpu_wait", "ygpu_seed_join", "ygpu_chain", "ygpu_dp_batch", "ygpu_dp_batch_ex",
     "yaha_session_open", "yaha_session_close", "yaha_session_error", "yaha_session_params",
     "yaha_session_index_view", "yaha_session_header", "yaha_session_next_batch", "yaha_session_emit", "yaha_session_postfilter_params", "yaha_session_emit_filtered",
@@ -184,6 +185,10 @@ def lib():
         L = C.CDLL(LIB_PATH)
         L.ygpu_last_error.restype = C.c_char_p
         L.yaha_session_error.restype = C.c_char_p
+        L.ygpu_bgzf_last_error.restype = C.c_char_p
+        L.ygpu_bgzf_last_error.argtypes = [C.c_void_p]
+        L.ygpu_bgzf_bound.restype = C.c_uint64
+        L.ygpu_bgzf_bound.argtypes = [C.c_uint64]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -505,6 +510,48 @@ class Context:
     def close(self):
         if self._h:
             lib().ygpu_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Bgzf:
+    """BGZF compression on the device (ygpu_bgzf_*): a handle of its own -- stream, device buffers, page-locked staging for inputs of up to max_in_bytes -- that
+    touches no Context.  compress(data) returns data's payloads of 65 280 bytes as whole BGZF blocks, one after the other, WITHOUT the end-of-file block (EOF):
+    gzip.decompress(b.compress(data) + Bgzf.EOF) == data."""
+
+    EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+    PAYLOAD_MAX = 65280
+
+    def __init__(self, max_in_bytes, device=0):
+        self._h = C.c_void_p()
+        rc = lib().ygpu_bgzf_open(device, C.c_uint64(max_in_bytes), C.byref(self._h))
+        if rc != 0:
+            msg = lib().ygpu_bgzf_last_error(self._h).decode() if self._h else ""
+            self.close()
+            raise RuntimeError("ygpu_bgzf_open failed: %d %s" % (rc, msg))
+
+    @staticmethod
+    def bound(n):
+        """Room compress() needs for n input bytes: ceil(n / 65280) * 65536 (ygpu_bgzf_bound)."""
+        return int(lib().ygpu_bgzf_bound(n))
+
+    def compress(self, data, out_cap=None):
+        data = bytes(data)
+        cap = self.bound(len(data)) if out_cap is None else out_cap
+        out = C.create_string_buffer(max(1, cap)); n = C.c_uint64()
+        rc = lib().ygpu_bgzf_compress(self._h, data, C.c_uint64(len(data)), out, C.c_uint64(cap), C.byref(n))
+        if rc != 0:
+            raise RuntimeError("ygpu_bgzf_compress failed: %d %s" % (rc, lib().ygpu_bgzf_last_error(self._h).decode()))
+        return out.raw[:n.value]
+
+    def close(self):
+        if self._h:
+            lib().ygpu_bgzf_close(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):

@@ -21,12 +21,14 @@ static void usage(FILE *o)
           "  yaha -g genome.{fa|fna|fasta} -c   (compress to genome.nib2 only)      yaha -g genome.nib2 -u   (back to genome.fasta)\n"
           "       (built on the GPU when one is visible and -S is 1; -cpuindex forces the host builder; the files are identical)\n\n"
           "Query alignment (hot path on MI355X):\n"
-          "  yaha -x indexFile [-q queryFile|(stdin)] [-o8|(-osh)|-oss outFile|(stdout)] [-t hostThreads (1)]\n"
+          "  yaha -x indexFile [-q queryFile|(stdin)] [-o8|(-osh)|-oss|-obh|-obs outFile|(stdout)] [-t hostThreads (1)]\n"
           "       [-gpus N (1)] [-ctx contextsPerGpu (3)] [-device D (0)] [-batch readsPerBatch (about 16 M bases)] [-dpf Y|N (Y: post-filter on the device)]\n"
           "  general : [-BW 5] [-G 50] [-H 650] [-M 25] [-MD 50] [-P 0.9] [-X 25]\n"
           "  scoring : [-AGS Y|N] [-GEC 2] [-GOC 5] [-MS 1] [-RC 3]\n"
           "  OQC     : [-OQC Y|N] [-BP 5] [-MGDP 5] [-MNO minMatch]   FBS: [-FBS Y|N] [-PRL 0.9] [-PSS 0.9]\n"
           "  -o8 modified Blast8, -osh SAM hard clipping, -oss SAM soft clipping.\n"
+          "  -obh BAM hard clipping, -obs BAM soft clipping: the records of -osh / -oss in BAM's layout, unsorted, in BGZF blocks deflated on the device\n"
+          "       (fixed Huffman codes; YAHA_HOST_BGZF=1: on the host).  The blocks' boundaries follow -batch and -ctx, the decompressed stream does not.\n"
           "  depth   : [-ocov depthFile|stdout] [-covbin basesPerBin (100)] [-covq minMapQ (0)]\n"
           "       read depth of the printed records along the reference (bases under M of the CIGAR) as bedGraph, written after the last alignment;\n"
           "       accumulated on the device behind its post-filter: 4 bytes a bin of device memory per GPU -- -covbin 1 on a 3.1 Gbp genome is 12.4 GB beside the\n"
@@ -91,11 +93,16 @@ int parseArgs(int argc, char **argv, Args &a)
         else if (is("-g")) { a.gfileName = val(); a.haveG = true; }
         // deliberate fix of Main.c:173-178, which turns these into "stdout" and then fails to open it
         else if (is("-q")) { const char *v = val(); a.qfileName = (!strcmp(v, "-") || !strcmp(v, "-stdin") || !strcmp(v, "stdin")) ? "stdin" : v; query = true; index = false; }
-        else if (is("-o8")) { a.outputBlast8 = true; a.outputSAM = false; const char *v = val(); a.ofileName = (!strcmp(v, "-stdout")) ? "stdout" : v; a.haveO = true; }
-        else if (is("-osh")) { a.outputBlast8 = false; a.outputSAM = true; a.hardClip = true; const char *v = val(); a.ofileName = (!strcmp(v, "-stdout")) ? "stdout" : v;
+        else if (is("-o8")) { a.outputBlast8 = true; a.outputSAM = false; a.outputBAM = false; const char *v = val(); a.ofileName = (!strcmp(v, "-stdout")) ? "stdout" : v;
             a.haveO = true; }
-        else if (is("-oss")) { a.outputBlast8 = false; a.outputSAM = true; a.hardClip = false; const char *v = val(); a.ofileName = (!strcmp(v, "-stdout")) ? "stdout" : v;
+        else if (is("-osh")) { a.outputBlast8 = false; a.outputSAM = true; a.outputBAM = false; a.hardClip = true; const char *v = val();
+            a.ofileName = (!strcmp(v, "-stdout")) ? "stdout" : v;
             a.haveO = true; }
+        else if (is("-oss")) { a.outputBlast8 = false; a.outputSAM = true; a.outputBAM = false; a.hardClip = false; const char *v = val();
+            a.ofileName = (!strcmp(v, "-stdout")) ? "stdout" : v; a.haveO = true; }
+        // BAM: the SAM writer's records in binary, hard (-obh) or soft (-obs) clipped; an output selector like the three above -- the last one given wins
+        else if (is("-obh") || is("-obs")) { a.outputBlast8 = false; a.outputSAM = true; a.outputBAM = true; a.hardClip = is("-obh"); const char *v = val();
+            a.ofileName = (!strcmp(v, "-stdout")) ? "stdout" : v; a.haveO = true; }
         else if (is("-t")) { if (!parseInt(val(), "-t", a.numThreads)) return 2; }
         else if (is("-v")) a.verbose = true;
         else if (is("-x")) { a.xfileName = val(); a.haveX = true; query = true; index = false; }
@@ -258,7 +265,7 @@ std::string samHeader(const Args &a, const Genome &g)                   // outpu
     std::string h = "@HD\tVN:1.0\n"; char buf[512];
     for (auto &s : g.seqs) { h += "@SQ\tSN:" + s.name; snprintf(buf, sizeof buf, "\tLN:%u\n", s.length); h += buf; }
     h += "@PG\tID:YAHA\tVN:0.1.83\tCL:yaha";
-    h += " -q " + a.qfileName + " -x " + a.xfileName; h += a.hardClip ? " -osh " : " -oss "; h += a.ofileName;
+    h += " -q " + a.qfileName + " -x " + a.xfileName; h += a.outputBAM ? (a.hardClip ? " -obh " : " -obs ") : a.hardClip ? " -osh " : " -oss "; h += a.ofileName;
     snprintf(buf, sizeof buf, " -t %d -BW %d -G %d -H %d -M %d -MD %d -P %4.2f -X %d", a.numThreads, a.bandWidth, a.maxGap, a.maxHits, a.minMatch, a.maxDesert, a.minIdentity,
         a.XCutoff); h += buf;
     if (a.affineGapScoring) { snprintf(buf, sizeof buf, " -AGS Y -GEC %d -GOC %d -MS %d -RC %d", a.GECost, a.GOCost, a.MScore, a.RCost); h += buf; } else h += " -AGS N";

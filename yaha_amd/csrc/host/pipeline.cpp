@@ -32,6 +32,7 @@ struct yaha_session {
     const JunctionTrack *junctions = nullptr; std::vector<ygpu_junction> *jnOut = nullptr; uint64_t jnReads = 0, jnSkipped = 0;
     // -oid: the formatters walk the records the device did not count (indels.cpp) into a list of their own, merged into the run's alleles once per batch
     const IndelTrack *indels = nullptr; IndelTrack::Local idLocal;
+    uint64_t bamRecords = 0;                                         // -obh / -obs: records written into the text (the formatters: per batch)
 };
 
 namespace yaha {
@@ -142,7 +143,8 @@ enum : unsigned { kJunctionsOnDevice = 1u << 31, kIndelsOnDevice = 1u << 30 };
 // one record of read i: its text, and its share of every binned track the device did not count it for
 static inline void emitRecord(yaha_session *s, uint32_t i, const OutClump &o, int primaryCount, Text &text, unsigned onDevice = 0)
 {
-    printClump(s->args, s->genome, s->reads[i], o, primaryCount, text);
+    if (s->args.outputBAM) { if (bamRecord(s->args, s->genome, s->reads[i], o, primaryCount, text)) s->bamRecords++; }
+    else printClump(s->args, s->genome, s->reads[i], o, primaryCount, text);
     for (size_t t = 0; t < s->tracks.size(); t++) if (!(onDevice >> t & 1u)) s->tracks[t]->add(o, s->reads[i]);
     if (s->indels && !(onDevice & kIndelsOnDevice)) s->indels->add(o, s->reads[i], s->idLocal);
 }
@@ -276,6 +278,13 @@ int runQueries(Args &a, FILE *log)
                                                                        : (uint64_t)16 << 20);
     std::vector<char> idEnabled((size_t)ngpu, 0);
     setvbuf(out, nullptr, _IONBF, 0);                                       // whole batches are written with one call each
+    // -obh / -obs: the header is BGZF blocks of its own from the host's encoder; every batch's records are compressed by the thread that formats them (bam.cpp) and
+    // the end-of-file block follows the last batch
+    BamStats bam;
+    if (A.outputBAM) {
+        const std::string raw = bamHeader(A, S->genome); Text packed; BgzfPacker hostPacker; hostPacker.packHost(raw.data(), raw.size(), packed, bam);
+        if (fwrite(packed.p, 1, packed.len, out) != packed.len) { fprintf(log, "Failure writing the output file.\n"); return 1; }
+    } else
     if (fputs(S->header.c_str(), out) < 0) { fprintf(log, "Failure writing the output file.\n"); return 1; }
     ygpu_params P; paramsFromArgs(A, P);
     ygpu_index_view V; yaha_session_index_view(S.get(), &V);
@@ -309,6 +318,8 @@ int runQueries(Args &a, FILE *log)
                    ResBuf clumpStart, ops, clumps; uint64_t nClumps = 0, nOps = 0; bool filtered = false; unsigned onDevice = 0; Text text;
                    // -obp: the junctions the device made of the batch and its statistics; the ones the formatter made, and its counts
                    std::vector<ygpu_junction> jnDev, jnHost; uint64_t jnDevStats[4] = {0, 0, 0, 0}, jnHostReads = 0, jnHostSkipped = 0;
+                   // -obh / -obs: the device the batch ran on, its records as BGZF blocks, the time their compression took
+                   int dev = 0; Text packed; double tPack = 0;
                    double tRead = 0, tDev = 0, tFmt = 0; };
     typedef std::unique_ptr<Batch> BatchP;
     struct Pool { std::mutex mu; std::vector<BatchP> free; BatchP get() { { std::lock_guard<std::mutex> lk(mu); if (!free.empty()) { BatchP b = std::move(free.back());
@@ -522,6 +533,7 @@ int runQueries(Args &a, FILE *log)
             const double w0 = now();
             if (!inQ.pop(b)) break;
             if (stop) { b->nReads = 0; fmtQ.push(std::move(b)); continue; }
+            b->dev = dev;
             const double t0 = now(); if (!first) usIdle += (uint64_t)((t0 - w0) * 1e3);
             ygpu_read_batch rb{(uint32_t)b->nReads, b->codes.data(), b->offsets.data()}; ygpu_result_batch res; memset(&res, 0, sizeof res); bool handedOver = false;
             auto hotPath = [&]() -> int {                                      // upload, run (+ post-filter), results straight into the batch's own buffers
@@ -581,6 +593,7 @@ int runQueries(Args &a, FILE *log)
             local.genome.maxROff = S->genome.maxROff;
         for (auto &T : tracks) local.tracks.push_back(T.track.get());
         local.junctions = junctions.get(); local.indels = indels.get();
+        std::unique_ptr<BgzfPacker> packer; if (A.outputBAM) packer.reset(new BgzfPacker);
         BatchP b;
         while (fmtQ.pop(b)) {
             const double t0 = now(); b->text.clear();
@@ -601,6 +614,13 @@ int runQueries(Args &a, FILE *log)
             b->jnHostReads = local.jnReads; b->jnHostSkipped = local.jnSkipped;
             if (indels) indels->merge(local.idLocal);
             b->tFmt = now() - t0;
+            if (packer) {                                                      // (a batch without records is no block: an empty one would read as the end of the file)
+                std::string perr; b->packed.clear();
+                const int prc = stop ? 0 : packer->pack(b->dev, b->text.p, b->text.len, b->packed, bam, perr);
+                if (prc != 0) { char m[640]; snprintf(m, sizeof m, "BGZF compression on device %d failed (%d): %s", b->dev, prc, perr.c_str()); fail(m); }
+                bam.records += local.bamRecords; local.bamRecords = 0;
+                b->tPack = now() - t0 - b->tFmt;
+            }
             outQ.push(std::move(b));
         }
         outQ.producerDone();
@@ -613,11 +633,14 @@ int runQueries(Args &a, FILE *log)
             while (!done.empty() && done.begin()->first == nextOut) {
                 BatchP w = std::move(done.begin()->second); done.erase(done.begin()); nextOut++; ticketsWritten = nextOut;
                 if (!stop) {
-                    if (w->text.len && fwrite(w->text.p, 1, w->text.len, out) != w->text.len) fail("Failure writing the output file");
+                    const Text &bytes = A.outputBAM ? w->packed : w->text;
+                    if (bytes.len && fwrite(bytes.p, 1, bytes.len, out) != bytes.len) fail("Failure writing the output file");
                     else { const double t = now(); if (nWritten == 0) { tFirstOut = t; nFirst = w->nReads; } tLastOut = t; nWritten += w->nReads; }
                     if (junctions && w->nReads) junctions->addBatch(w->jnDev.data(), w->jnDev.size(), w->jnDevStats, w->jnHost, w->jnHostReads, w->jnHostSkipped);
                     if (timing) fprintf(stderr, "[yaha] ticket %llu: %zu reads  parse %.1f  device (upload, run, collect) %.1f  format %.1f ms  written at %.1f\n",
                         (unsigned long long)w->ticket, w->nReads, w->tRead, w->tDev, w->tFmt, now() - tEnter);
+                    if (timing && A.outputBAM) fprintf(stderr, "[yaha] ticket %llu: %zu bytes of records compressed to %zu in %.1f ms (wait for the blocks included)\n",
+                        (unsigned long long)w->ticket, w->text.len, w->packed.len, w->tPack);
                 }
                 pool.put(std::move(w));
             }
@@ -636,6 +659,9 @@ int runQueries(Args &a, FILE *log)
     if (!stop && ticketsWritten.load() != ticketsIssued.load()) {
         fprintf(log, "internal error: %llu of %llu batches were written -- the output is incomplete.\n", (unsigned long long)ticketsWritten.load(),
         (unsigned long long)ticketsIssued.load()); rcAll = 1; }
+    // -obh / -obs: the end-of-file block, once, after the last batch of a run that got there
+    if (A.outputBAM && !stop && rcAll == 0) { Text eof; bgzfEof(eof); bam.bytesWritten += eof.len; if (fwrite(eof.p, 1, eof.len, out) != eof.len) {
+        fprintf(log, "Failure writing the output file.\n"); rcAll = 1; } }
     // The command line (csrc/main.cpp) leaves right after this function: it sets YAHA_FAST_EXIT and lets the process exit release the device memory and the
     // page-locked buffers in one go, instead of a hipFree per buffer (a second of waiting at the end of every run, measured).  Library users get the orderly path.
     // the binned tracks, in the table's order: every image's array added to the host's, the file written after the last alignment
@@ -683,7 +709,7 @@ int runQueries(Args &a, FILE *log)
         std::string per = "[";
         for (int k = 0; k < nDev; k++) { char t[32]; snprintf(t, sizeof t, "%s%llu", k ? ", " : "", (unsigned long long)devReads[k].load()); per += t; }
         per += "]";
-        char dstat[1280] = "";
+        char dstat[1664] = "";
         for (auto &T : tracks) { const size_t at = strlen(dstat); const BinnedTrack &t = *T.track;
             snprintf(dstat + at, sizeof dstat - at, T.statsFmt, (unsigned long long)t.nBins, (unsigned long long)t.devRecords, (unsigned long long)t.hostRecords,
                 (unsigned long long)t.sum());
@@ -696,6 +722,11 @@ int runQueries(Args &a, FILE *log)
                 "\"indel_lines\": %llu, \"indel_drains\": %llu, \"indel_lost\": %llu", (unsigned long long)indels->devRecords, (unsigned long long)indels->hostRecords,
                 (unsigned long long)(indels->devEvents + indels->hostEvents), (unsigned long long)indels->alleles.size(), (unsigned long long)indels->nLines,
                 (unsigned long long)indels->drains, (unsigned long long)indels->devLost); }
+        if (A.outputBAM) { const size_t at = strlen(dstat);
+            snprintf(dstat + at, sizeof dstat - at, ", \"bam_records\": %llu, \"bam_bytes_raw\": %llu, \"bam_bytes_written\": %llu, \"bam_blocks\": %llu, "
+                "\"bam_blocks_stored\": %llu, \"bam_device_batches\": %llu, \"bam_host_batches\": %llu", (unsigned long long)bam.records.load(),
+                (unsigned long long)bam.bytesRaw.load(), (unsigned long long)bam.bytesWritten.load(), (unsigned long long)bam.blocks.load(),
+                (unsigned long long)bam.blocksStored.load(), (unsigned long long)bam.deviceBatches.load(), (unsigned long long)bam.hostBatches.load()); }
         fprintf(stderr, "[yaha] stats {\"reads\": %llu, \"contexts_up_ms\": %.1f, \"first_batch_written_ms\": %.1f, \"last_batch_written_ms\": %.1f, \"total_ms\": %.1f, "
             "\"steady_reads_per_s\": %.0f, \"cpus\": %d, \"formatters\": %d, \"parsers\": %d, \"gpus\": %d, \"ctx_per_gpu\": %d, \"ctx_left_out\": %d, "
             "\"reads_per_device\": %s, \"context_thread_ms_per_batch\": {\"wait_for_a_batch\": %.2f, \"upload\": %.2f, \"run\": %.2f, \"wait_for_filter_thread\": %.2f, "

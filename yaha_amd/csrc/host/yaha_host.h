@@ -9,6 +9,8 @@
 #include <string>
 #include <map>
 #include <mutex>
+#include <atomic>
+#include <algorithm>
 #include <vector>
 #include <memory>
 #include <cstdlib>
@@ -72,6 +74,7 @@ struct Args {
     bool affineGapScoring = true; int GOCost = 5, GECost = 2, RCost = 3, MScore = 1, XCutoff = 25; int minExtLength = 0;
     bool OQC = true; int OQCMinNonOverlap = -1, BPCost = 5, maxBPLog = 5; bool FBS = false; float FBS_PSLength = 0.90f, FBS_PSScore = 0.90f;
     int maxQueryLength = 32000; bool verbose = false, outputBlast8 = false, outputSAM = true, hardClip = true;
+    bool outputBAM = false;                              // -obh / -obs: the SAM writer's records in BAM's layout, BGZF-compressed (bam.cpp); outputSAM stays set
     // extensions of this implementation (not in the reference CLI)
     int batchReads = 0; int device = 0; int gpus = 1; int ctxPerGpu = 3; bool cpuIndex = false; bool devicePostFilter = true;      // batchReads 0: batches of ~16 M bases
     // read-depth track: -ocov FILE (bedGraph), -covbin B (bases a bin), -covq Q (records below this mapping quality cover nothing)
@@ -147,6 +150,26 @@ struct Text {
     void grow(size_t need) { size_t c = cap ? cap : (1u << 16); while (c < need) c += c / 2; char *q = (char *)realloc(p, c); if (!q) throw std::bad_alloc(); p = q; cap = c; }
 };
 void printClump(const Args &a, const Genome &g, const Read &r, const OutClump &oc, int primaryCount, Text &out);
+
+// ---- BAM output (-obh / -obs; bam.cpp, ../bgzf_core.h) ----------------------------------------------------------------------------------------------------------
+// The uncompressed header: "BAM\1", samHeader's text, the genome's sequences.  A record: printClump's record in BAM's layout, appended to out (false: the
+// clump spans two sequences and is dropped, as printClump drops it).
+std::string bamHeader(const Args &a, const Genome &g);
+bool bamRecord(const Args &a, const Genome &g, const Read &r, const OutClump &oc, int primaryCount, Text &out);
+struct BamStats { std::atomic<uint64_t> records{0}, bytesRaw{0}, bytesWritten{0}, blocks{0}, blocksStored{0}, deviceBatches{0}, hostBatches{0}; };
+// What a formatter thread compresses its batches with: a device handle of its own (ygpu_bgzf_*, looked up weakly as the tracks' entry points are), opened
+// when first needed and reopened when a batch outgrows it, or the host's encoder -- without the entry points, when no handle can be opened, with
+// YAHA_HOST_BGZF=1.  No end-of-file block is written here (bgzfEof: the writer's, once).
+struct BgzfPacker {
+    BgzfPacker(); ~BgzfPacker(); BgzfPacker(const BgzfPacker &) = delete; BgzfPacker &operator=(const BgzfPacker &) = delete;
+    static bool deviceEntryPoints();                                      // does this build have ygpu_bgzf_*?
+    // in[0 .. n) as whole BGZF blocks into out (cleared first); 0, or the device's error code with err = the handle's message
+    int  pack(int device, const char *in, size_t n, Text &out, BamStats &st, std::string &err);
+    void packHost(const char *in, size_t n, Text &out, BamStats &st);     // the host's encoder, whatever the build has
+  private:
+    struct Impl; Impl *impl;
+};
+void bgzfEof(Text &out);                                                  // appends the 28-byte end-of-file block
 
 // ---- the binned tracks: read depth (-ocov), the evidence track (-oev) and the allele pileup (-opu) (depth.cpp, events.cpp, pileup.cpp; ../*_core.h) --------
 // The host's array of a track, in the layout the device uses (one routine a kind, *_core.h): `channels` uint32 a bin, bin-major.  The formatter threads add the
