@@ -1,17 +1,20 @@
 """CPU tier: BAM output (-obh / -obs) through the whole command line -- host sources, main.cpp and the test double tests/fixtures/oracle_device.cpp, which has no
 ygpu_bgzf_*: every block here comes from the host's encoder (csrc/bgzf_core.h, the source the device kernel compiles as well) -- and that encoder alone as a
 program of its own (tests/fixtures/bgzf_driver.cpp), plainly and under AddressSanitizer + UBSan.  Everything is judged by tests/bam_oracle.py: a strict BGZF
-reader, and the SAM text a BAM stream stands for against the golden SAM of the same options."""
+reader, and the SAM text a BAM stream stands for against the golden SAM of the same options -- and by tests/bgzf_model.py: the blocks both encoders must
+write, bit for bit, from the written contract and RFC 1951's tables (the host's here; the device's in tests/test_gpu_bgzf.py, on the same inputs)."""
 import glob
 import gzip
 import json
 import os
 import random
 import subprocess
+import zlib
 
 import pytest
 
 import bam_oracle as bo
+import bgzf_model as bm
 from conftest import GOLDEN, ROOT, golden_lines, strip_pg
 
 HOST = os.path.join(ROOT, "yaha_amd", "csrc", "host")
@@ -59,10 +62,13 @@ def test_command_line_bam_is_the_golden_sam(exe, work, index11, tmp_path, name, 
     _o, st = _run(exe, ["-x", index11, "-q", q, "-obh", out])
     raw1 = check_bam(open(out, "rb").read(), golden_lines(name), st, "-obh")
     assert st["bam_device_batches"] == 0 and st["bam_host_batches"] > 0              # (the double has no device encoder)
+    data = open(out, "rb").read()
+    assert blocks_are_modelled(data[:-28], st["bam_blocks"]) == st["bam_blocks"]     # every block: the host model's of its own payload
     # the blocks follow -batch and -ctx, the decompressed stream does not
     _o, st = _run(exe, ["-x", index11, "-q", q, "-obh", out, "-ctx", "2", "-batch", "64"], env={"YTEST_DEVICES": "1"})
     data = open(out, "rb").read()
     assert check_bam(data, golden_lines(name), st, "-obh") == raw1
+    assert blocks_are_modelled(data[:-28], st["bam_blocks"]) == st["bam_blocks"]
     _o, st1 = _run(exe, ["-x", index11, "-q", q, "-obh", out, "-ctx", "1"])
     assert bo.read_file(open(out, "rb").read())[0] == raw1
     # soft clipping against -oss of the same binary; to standard output
@@ -101,7 +107,110 @@ def byte_sets(real_bam=None):
     sets["random"] = random.Random(1).randbytes(P)
     if real_bam is not None:
         sets["bam"] = real_bam
+    sets.update(_built_sets())
     return sets
+
+
+def _unique_bytes(rnd, n, lo, hi, seen):
+    """n bytes of lo .. hi - 1 no four of which occur twice (seen: the four-byte strings so far, extended here): nothing in them can be matched."""
+    out = bytearray()
+    while len(out) < n:
+        out.append(rnd.randrange(lo, hi))
+        if len(out) >= 4:
+            if bytes(out[-4:]) in seen:
+                out.pop()
+            else:
+                seen.add(bytes(out[-4:]))
+    return bytes(out)
+
+
+def _ladder():
+    """Runs of L + 1 equal bytes for L = 4 .. 258, a byte of their own each (from both sides of 144), one breaker byte that no run uses behind each: a literal
+    and ONE match of length L at distance 1 a run, so every match length, starting at lane and chunk offsets that drift through the tiles."""
+    run_byte = {L: L * 37 % 256 for L in range(4, 259)}                              # 37 is odd: 255 different bytes
+    breaker = (set(range(256)) - set(run_byte.values())).pop()
+    return b"".join(bytes([run_byte[L]]) * (L + 1) + bytes([breaker]) for L in range(4, 259))
+
+
+DIST_EDGES = sorted({d for c in range(30) for d in (bm.DIST_BASE[c], bm.DIST_BASE[c] + (1 << bm.DIST_EXTRA[c]) - 1)})   # the first and last distance of every code
+
+
+def _dists():
+    """A payload of zeros with, for the first and the last distance D of every distance code and for 32 769, a marker of eight bytes and its copy D behind it
+    (D <= 8: D bytes and their periodic continuation).  Where D < 256 the copy starts a tile, so that the device's table (earlier tiles only) holds the
+    marker.  The table keeps ONE position per hash: the filler is a constant run, and a marker is drawn again until no four bytes in or around it share a
+    hash with different four bytes of the payload."""
+    rnd = random.Random(17); n = 36864
+    buf, busy, grams = bytearray(n), bytearray(n), {bm.hashes(bytes(4))[0]: bytes(4)}
+    for d in [x for x in DIST_EDGES if x > 1] + [32769]:
+        k = min(d, 8)
+        s = next(s for s in range(16, n) if (d >= 256 or (s + d) % 256 == 0) and not any(busy[s - 8:s + k + 16]) and not any(busy[s + d - 8:s + d + 16]))
+        while True:
+            unit = bytes(rnd.sample(range(1, 256), k))
+            trial = bytearray(buf); trial[s:s + k] = unit; trial[s + d:s + d + 8] = (unit * 8)[:8]
+            new = {}
+            for a, b in ((s - 3, s + k + 3), (s + d - 3, s + d + 11)):
+                for h, q in zip(bm.hashes(bytes(trial[a:b + 3])), range(a, b)):
+                    new.setdefault(h, set()).add(bytes(trial[q:q + 4]))
+            if all(len(g) == 1 and grams.get(h, min(g)) == min(g) for h, g in new.items()):
+                break
+        buf = trial
+        for h, g in new.items():
+            grams[h] = min(g)
+        busy[s:s + k] = b"\1" * k; busy[s + d:s + d + 8] = b"\1" * 8
+    return bytes(buf)
+
+
+def _high_9bit():
+    """Bytes of 144 and above only.  Three tiles that nothing matches (256 nine-bit literals a tile), 4-letter filler up to position 16 384, 255 more
+    unmatched bytes and then, in the tile's last lane, a copy of the payload's first 200 bytes: 255 x 9 bits and a match of 8 + 5 + 5 + 13 = 31, the most a
+    tile can add to the window.  More filler, so that the block deflates."""
+    for seed in range(13, 100):
+        rnd = random.Random(seed); seen = set()
+        first = _unique_bytes(rnd, 768, 144, 256, seen)
+        fill = bytes(rnd.choice(b"\x90\xA5\xC3\xFF") for _ in range(16384 - 768 + 4096))
+        data = first + fill[:16384 - 768] + _unique_bytes(rnd, 255, 144, 256, seen) + first[:200] + fill[16384 - 768:]
+        h = bm.hashes(data[:16384 + 255 + 4])
+        if h[0] not in h[1:16384 + 255]:                                             # the table still holds position 0 when the copy is reached
+            return data
+    raise AssertionError("no seed keeps the first four bytes' slot")
+
+
+def _tile_edges():
+    """Matches of length 4 and 258 (runs: a literal, then distance 1) that start at tile offsets 0, 1, 63, 64 and 255, four tiles a case, bytes below 144
+    that nothing matches between them.  A match of 258 from offset 255 covers the whole next tile: no token starts there."""
+    rnd = random.Random(11); seen = set(); out = bytearray(); run = 246
+    for length in (4, 258):
+        for off in (0, 1, 63, 64, 255):
+            out += _unique_bytes(rnd, 256 + off - 1, 0, 144, seen) + bytes([run]) * (length + 1)
+            out += _unique_bytes(rnd, -len(out) % 1024, 0, 144, seen); run += 1
+    return bytes(out)
+
+
+def _built_sets():
+    P = bo.PAYLOAD_MAX; rnd = random.Random(19)
+    sets = {"ladder": _ladder(), "dists": _dists(), "high_9bit": _high_9bit(), "tile_edges": _tile_edges()}
+    # one run, one short period across two payload boundaries: a match is cut at its payload's end with equal bytes behind it, and none reaches back
+    sets["zeros_2P+5"] = bytes(2 * P + 5)
+    sets["period7_2P+5"] = (b"\x07\x90\xFFabcd" * (2 * P // 7 + 2))[:2 * P + 5]
+    # two tiles of text, then a last tile of 1, 2, 3 bytes (nine-bit literals) none of which can be hashed
+    text = bytes(rnd.choice(b"ACGT") for _ in range(512))
+    for j in (1, 2, 3):
+        sets["tail_%d" % j] = text + bytes([0xF0 + i for i in range(j)])
+    return sets
+
+
+HOST_BLOCKS, DEVICE_BLOCKS = {}, {}                                                   # payload -> the model's block (bm.stream's cache), shared by the tests of a run
+
+
+def blocks_are_modelled(data, n_host):
+    """data: BGZF blocks; the first n_host must be the host model's block of their own payload, every later one the device model's."""
+    raw = bm.split_blocks(data); read = bo.blocks(data)
+    assert len(raw) == len(read) and b"".join(raw) == data
+    for i, (blk, (payload, _size, _stored)) in enumerate(zip(raw, read)):
+        want = bm.stream(payload, bm.host_tokens, HOST_BLOCKS) if i < n_host else bm.stream(payload, bm.device_tokens, DEVICE_BLOCKS)
+        assert blk == want, "block %d of %d (%s model, %d payload bytes)" % (i, len(raw), "host" if i < n_host else "device", len(payload))
+    return len(raw)
 
 
 @pytest.fixture(scope="module")
@@ -131,6 +240,7 @@ def test_host_encoder_on_byte_sets(drivers, tmp_path):
             assert info["blocks"] == len(bl) == -(-len(data) // bo.PAYLOAD_MAX) and info["stored"] == sum(1 for _p, _s, st in bl if st)
             assert all(size <= min(bo.BLOCK_MAX, 18 + 5 + len(pl) + 8) for pl, size, _st in bl), name      # never larger than the stored form
             assert outs.setdefault(name, got) == got                                  # the two builds write the same bytes
+            assert got[:-28] == bm.stream(data, bm.host_tokens, HOST_BLOCKS), name    # ... and they are the bytes the contract gives, bit for bit
     assert [st for _p, _s, st in bo.read_file(outs["random"])[1]] == [True]           # what does not compress is stored
     # a literal, then 254 matches of length 258 (the last one shorter), 31 bits each at the very most, and the framing of block and end-of-file block
     assert len(outs["zeros"]) < 254 * 31 // 8 + 64 + 28
@@ -138,3 +248,92 @@ def test_host_encoder_on_byte_sets(drivers, tmp_path):
     assert len(outs["period_32768"]) < len(outs["period_32769"])
     assert [st for _p, _s, st in bo.read_file(outs["period_32769"])[1]] == [True]     # ... one past it no match may be used: random bytes, stored
     assert len(outs["bam"]) < len(real)                                               # ASCII literals cost 8 bits, every repeated name or tag saves some
+
+
+# ---- the model of both encoders (tests/bgzf_model.py) -----------------------------------------------------------------------------------------------------------------
+def test_model_blocks_are_valid_and_the_sets_reach_every_code():
+    """Every block the model makes, for either parse, goes through the strict reader; and the inputs reach what they were built for -- asserted from the model
+    alone, for the device's parse and separately for the host's (which reaches every code as well: distances 1 .. 3 through runs and short periods)."""
+    sets = byte_sets()
+    for fn, cache in ((bm.device_tokens, DEVICE_BLOCKS), (bm.host_tokens, HOST_BLOCKS)):
+        who = fn.__name__
+        lengths, dists, codes, rejected, per_set = set(), set(), set(), 0, {}
+        for name, data in sorted(sets.items()):
+            at = 0
+            for pl in bm.payloads(data):
+                info = {}; tokens = fn(pl, info); st = bm.stats(pl, tokens)
+                blk = cache.setdefault(pl, bm.block(pl, tokens))
+                assert bo.blocks(blk) == [(pl, len(blk), blk[18] & 6 == 0)], (who, name)
+                assert all(d <= min(bm.MAX_DIST, p) and bm.MIN_MATCH <= l <= min(bm.MAX_MATCH, len(pl) - p) for p, (l, d) in st["starts"].items()), (who, name)
+                lengths |= st["lengths"]; dists |= st["dists"]; codes |= st["dist_codes"]; rejected += info["rejected"]
+                per_set.setdefault(name, []).append((st, info, blk[18] & 6 == 0, at)); at += len(pl)
+            assert bm.stream(data, fn, cache) == b"".join(cache[pl] for pl in bm.payloads(data))
+        assert lengths == set(range(4, 259)), (who, sorted(set(range(4, 259)) - lengths))
+        assert codes == set(range(30)), (who, sorted(set(range(30)) - codes))
+        assert 32768 in dists and rejected >= 1, who
+        # ladder: one literal and one match of L at distance 1 a run (and the breaker)
+        (st, _i, stored, _at), = per_set["ladder"]
+        assert not stored and st["lengths"] == set(range(4, 259)) and st["dists"] == {1}, who
+        assert {p % 64 for p in st["starts"]} == set(range(64)), who               # the cursor lands on every lane of a chunk, its edges included
+        # dists: every planted distance is used, and the one candidate at 32 769 (its eight bytes: five windows of four, and the zeros before) is passed over
+        (st, info, stored, _at), = per_set["dists"]
+        assert not stored and st["dists"] >= set(DIST_EDGES) and max(st["dists"]) == 32768 and info["rejected"] >= 1, (who, sorted(set(DIST_EDGES) - st["dists"]))
+        # high_9bit: deflated although nine-bit literals dominate its first tiles; the tile of 255 such literals and a 31-bit match
+        (st, _i, stored, _at), = per_set["high_9bit"]
+        assert not stored and max(st["tile_bits"]) >= 2300 and max(st["tile_bits"]) == 255 * 9 + 31 and st["nine_bit"] >= 768 + 255, (who, max(st["tile_bits"]))
+        # tile_edges: the ten matches where they were put, and a tile inside the payload in which no token starts
+        (st, _i, stored, _at), = per_set["tile_edges"]
+        want = {1024 * i + 256 + off: (length, 1) for i, (length, off) in enumerate((l, o) for l in (4, 258) for o in (0, 1, 63, 64, 255))}
+        assert not stored and st["starts"] == want and 0 in st["tile_bits"][:-1], who
+        # a run or a period across payload boundaries: every payload starts with literals (nothing reaches back: the host's first match is one period in, the
+        # device's too for a run, else with its second tile) and ends inside a match that is cut there, shorter than 258, with equal bytes behind it
+        for name, period in (("zeros_2P+5", 1), ("period7_2P+5", 7)):
+            assert len(per_set[name]) == 3
+            for st, _i, stored, at in per_set[name]:
+                size = min(bo.PAYLOAD_MAX, len(sets[name]) - at)
+                if size < period + bm.MIN_MATCH:
+                    assert not st["starts"], (who, name)
+                    continue
+                assert not stored and (st["dists"] == {period} if fn is bm.host_tokens else all(d % period == 0 for d in st["dists"])), (who, name)
+                assert min(st["starts"]) == (period if fn is bm.host_tokens or period == 1 else bm.TILE), (who, name)
+                last = max(st["starts"])
+                assert last + st["starts"][last][0] == size and (size < bo.PAYLOAD_MAX or st["starts"][last][0] < bm.MAX_MATCH), (who, name)
+        for j in (1, 2, 3):
+            (st, _i, stored, _at), = per_set["tail_%d" % j]
+            assert not stored and st["tile_bits"][-1] == 9 * j and len(st["tile_bits"]) == 3, (who, j)
+    # the two parses differ: the device sees no position of the cursor's own tile
+    assert DEVICE_BLOCKS[sets["acgt_255"]] != HOST_BLOCKS[sets["acgt_255"]]
+
+
+@pytest.fixture(scope="module")
+def codes_driver(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("bgzf_codes") / "bgzf_codes_driver")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", out, os.path.join(ROOT, "tests", "fixtures", "bgzf_codes_driver.cpp")])
+    return out
+
+
+def test_code_tables_exhaustively(codes_driver):
+    """literalBits and matchBits of csrc/bgzf_core.h against RFC 1951's tables (tests/bgzf_model.py): every literal, every length with the first and last
+    distance of every distance code, every distance with the shortest and the longest match."""
+    lines = subprocess.run([codes_driver, "codes"] + [str(d) for d in DIST_EDGES], stdout=subprocess.PIPE, check=True).stdout.decode().split("\n")[:-1]
+    lit = [tuple(map(int, l.split()[1:])) for l in lines if l[0] == "L"]
+    assert lit == [(b,) + bm.literal_code(b) for b in range(256)]
+    assert all((n == 8) == (b < 144) and n in (8, 9) for b, _v, n in lit)
+    got = [tuple(map(int, l.split()[1:])) for l in lines if l[0] == "M"]
+    asked = [(length, d) for length in range(3, 259) for d in DIST_EDGES] + [(length, d) for d in range(1, 32769) for length in (4, 258)]
+    assert len(DIST_EDGES) == 56 and len(got) == len(asked) == len(lines) - 256
+    bad = [(g, bm.match_code(*a)) for g, a in zip(got, asked) if g != a + bm.match_code(*a)]
+    assert not bad, bad[:5]
+    assert max(n for _l, _d, _v, n in got) == 31 and all(v < 1 << n for _l, _d, v, n in got)
+
+
+def test_crc_shares_join(codes_driver, tmp_path):
+    """crc32(A B) = crcShift(crc32(A), |B|) ^ crc32(B): the algebra the kernel's 256 shares rest on, against zlib, with |A|, |B| around a lane's piece and a
+    whole payload."""
+    data = random.Random(23).randbytes(2 * 65279); src = str(tmp_path / "crc.bin")
+    open(src, "wb").write(data)
+    rows = [tuple(map(int, l.split()[1:])) for l in subprocess.run([codes_driver, "crc", src], stdout=subprocess.PIPE, check=True).stdout.decode().split("\n")[:-1]]
+    sizes = (0, 1, 255, 256, 257, 65279)
+    assert [r[:2] for r in rows] == [(a, b) for a in sizes for b in sizes]
+    for a, b, ca, cb, joined in rows:
+        assert (ca, cb, joined) == (zlib.crc32(data[:a]), zlib.crc32(data[a:a + b]), zlib.crc32(data[:a + b])), (a, b)
