@@ -18,6 +18,21 @@ static void diagJointHist(ygpu_ctx *ctx, uint32_t J)
                     "the rest: banded %llu (W <= 32 within the band kernels' limits: %llu, %llu cells), full %llu; "
                     "W 17-24 / 25-32 / 33-40 / 41-48 / more: %llu %llu %llu %llu %llu\n",
             nj[0], nj[1], nj[2], nj[3], cj[0], cj[1], cj[2], cj[3], b3, b3lim, c3lim, f3, wh[0], wh[1], wh[2], wh[3], wh[4]);
+    // what phase 1's two passes see: the roots by fragments and by DP joints (k_p1_roots finishes those without one), the DP joints by the length of their op
+    // list, the pure diagonals by length (the mask holds 64 bases)
+    const uint32_t NC = ctx->nClumps; std::vector<uint32_t> jb((size_t)NC + 1); hipMemcpy(jb.data(), ctx->jointBase.p, 4ull * (NC + 1), hipMemcpyDeviceToHost);
+    unsigned long long fr[6] = {0}, noDP = 0, noDPmulti = 0, oh[17] = {0}, dh[7] = {0}, nDiag = 0, nDPj = 0; const unsigned de[6] = {4, 8, 16, 32, 64, 128};
+    for (uint32_t r = 0; r < NC; r++) {
+        const uint32_t nj2 = jb[r + 1] - jb[r]; fr[std::min(5u, nj2)]++; bool dp = false;
+        for (uint32_t k = jb[r]; k < jb[r + 1] && k < J; k++) dp |= hj[k].kind == JK_DP;
+        noDP += !dp; noDPmulti += !dp && nj2 > 0;
+    }
+    for (auto &j : hj) { if (j.kind == JK_DP) { nDPj++; oh[j.nOps <= 15 ? j.nOps : 16]++; }
+        if (j.kind == JK_DIAG) { nDiag++; int b = 0; while (b < 6 && j.qGap > de[b]) b++; dh[b]++; } }
+    fprintf(stderr, "[ygpu] roots %u by fragments (1, 2, 3, 4, 5, more): %llu %llu %llu %llu %llu %llu; without a DP joint %llu (%.1f%%; %llu of them with joints)\n", NC,
+            fr[0], fr[1], fr[2], fr[3], fr[4], fr[5], noDP, 100.0 * noDP / std::max(1u, NC), noDPmulti);
+    fprintf(stderr, "[ygpu] DP joints %llu by ops (0 .. 15, more):", nDPj); for (int k = 0; k < 17; k++) fprintf(stderr, " %llu", oh[k]);
+    fprintf(stderr, "; pure diagonals %llu by length (<= 4, 8, 16, 32, 64, 128, more):", nDiag); for (int k = 0; k < 7; k++) fprintf(stderr, " %llu", dh[k]); fprintf(stderr, "\n");
 }
 
 // YGPU_COUNT_DUPS: how many extension problems of the batch are exact duplicates (direction, strand, read, rOff, qOff, qLen)?

@@ -79,7 +79,8 @@ struct DevBuf {
 // words of ygpu_ctx::counters (device): queue heads, arena counts, list lengths of one batch
 enum {
     CNT_NMULTI = 0, CNT_MAXN, CNT_CLUMPS, CNT_CFRAGS, CNT_QCHAIN, CNT_QALIGN, CNT_OUTCLUMPS, CNT_OUTOPS, CNT_QDP, CNT_DPOPS, CNT_NBIG, CNT_QBIG,
-    CNT_STATEOPS, CNT_EXTOPS, CNT_QEXT, CNT_SLOW, CNT_NDP, CNT_NDP16, CNT_GAPOPS, CNT_PAD_EVEN, CNT_NMULTI2 /* (multi | tiny << 32), (small | middle << 32): two 64-bit words */,
+    CNT_STATEOPS, CNT_EXTOPS, CNT_QEXT, CNT_SLOW, CNT_NDP, CNT_NDP16, CNT_GAPOPS, CNT_NPEND,
+    CNT_NMULTI2 /* (multi | tiny << 32), (small | middle << 32): two 64-bit words */,
         CNT_NTINY, CNT_NSMALL, CNT_NMID, CNT_NB12, CNT_NB16,
         CNT_NB24,
     CNT_SEGC,                            // YD_SEG_NCLASS + 1 words: the segments of the workgroup-sort classes, the long ones
@@ -160,7 +161,7 @@ struct ygpu_ctx {
     DevBuf rootState, stateOps, extProbs, rowsBound, stripOff, extRes, extTrace, chunkCnt;
     DevBuf memoKeys, memoCount, probs2, rowsBound2, stripOff2, extRes2, extTrace2, splitScratch, fallList;
     DevBuf keys2a, keys2b, vals2a, vals2b, extKeys, extVals, extKeys2, extOrder, slowList;
-    DevBuf gapScratch, jointCount, jointBase, joints, sortKeys, sortVals, sortKeys2, sortVals2, gapOps;
+    DevBuf gapScratch, jointCount, jointBase, joints, sortKeys, sortVals, sortKeys2, sortVals2, gapOps, pendList;
     DevBuf waveChunks, extOps, traceCnt, rowsClock;
     // counters and work words
     DevBuf counters, ctr, errFlag, scanState, bucketWork;

@@ -1,10 +1,10 @@
 // dp_stage.h -- glue for the stage-level DP entry (ygpu_dp_batch) when it runs the PRODUCTION lane kernels: k_ext_rows / k_ext_trace for the X-drop
-// extensions, the pure-diagonal shortcut of k_p1_joints and k_gap_lanes<16|32> / k_gap_wave for the gap fills -- exactly the kernels, launch shapes and
+// extensions, the pure-diagonal shortcut of k_p1_roots and k_gap_lanes<16|32> / k_gap_wave for the gap fills -- exactly the kernels, launch shapes and
 // data layouts ygpu_run uses at -BW 5 -- so that every findAffineGapScore call (SW.cpp:798-1208, wrappers :462-547) can be compared one by one.
 #pragma once
 #include "split_lanes.h"
 
-// classify a gap problem as k_p1_joints does (phase_lanes.h): pure diagonal or DP; sort key = (class, strip width, rows)
+// classify a gap problem as k_p1_roots does (phase_lanes.h): pure diagonal or DP; sort key = (class, strip width, rows)
 __global__ void k_dp_classify(DevParams P, const uint8_t *bases, const uint8_t *fwd, const uint8_t *rev, JointRec *joints, uint32_t n, uint32_t *keys, uint32_t *diagOps)
 {
     YD_HIGH_PRIO();
@@ -59,7 +59,7 @@ __global__ void k_dp_gather_gap(DevParams P, const uint8_t *bases, const uint8_t
             if (c == pc) pl++; else { if (pc >= 0) outOps[w++] = ((uint32_t)(uint8_t)codes[pc] << 16) | (uint32_t)pl; pc = c; pl = 1; }
         }
         if (pc >= 0) outOps[w++] = ((uint32_t)(uint8_t)codes[pc] << 16) | (uint32_t)pl;
-    } else for (uint32_t k = 0; k < j.nOps; k++) { const uint32_t op = gapOps[j.opsOff + k];
+    } else for (uint32_t k = 0; k < j.nOps; k++) { const uint32_t op = (j.flags & JF_INLINE) ? jointInlineOp(j, (int)k) : gapOps[j.opsOff + k];
         outOps[o.op_start + k] = ((uint32_t)(uint8_t)codes[opCode(op) & 3] << 16) | (uint32_t)opLen(op); }
     out[dst[t]] = o;
 }

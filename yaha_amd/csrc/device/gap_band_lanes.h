@@ -121,20 +121,6 @@ __global__ void __launch_bounds__(64) k_gap_band(AlignArgs A, PhaseArgs X)
             tmp[n * 64] = opMake(prev, acc2); n++;
             nT = n;
         }
-        // op slots: wave prefix sum of nT (as k_gap_lanes)
-        int incl = nT;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { int v = __shfl_up(incl, d, 64); if (lane >= d) incl += v; }
-        const int total = __shfl(incl, 63, 64); unsigned ob = 0;
-        if (lane == 63 && total) ob = atomicAdd(X.gapOpsCount, (unsigned)total);
-        ob = (unsigned)__shfl((int)ob, 63, 64);
-        if (live) {
-            const unsigned off = ob + (unsigned)(incl - nT);
-            if ((unsigned long long)off + (unsigned)nT > (unsigned long long)X.gapOpsCap) atomicCAS(A.errFlag, 0, (int)YERR_OUT);
-            else {
-                for (int k = 0; k < nT; k++) X.gapOps[off + k] = tmp[(nT - 1 - k) * 64];    // list order
-                JointRec *jp = X.joints + ji; jp->opsOff = off; jp->nOps = (uint16_t)nT; jp->score = score; jp->cells = cells;
-            }
-        }
+        gapListOut(A, X, lane, live, ji, tmp, nT, score, cells);
     }
 }

@@ -2,13 +2,14 @@
 //
 //   phase 1 = alignClump up to the extensions (AlignHelpers.c:205-272, AlignExtFrag.cpp:164-234)
 //     k_joint_counts   joints (fragment pairs) per root clump -> scan -> joint slots
-//     k_p1_joints      lane per root: the exact-match extensions of every joint, then the joint's gap is classified:
-//                      nothing / one D, I or R op / pure diagonal (see below) / a DP problem (sort key = strip width, rows)
+//     k_p1_roots       lane per root: the exact-match extensions of every joint, then the joint's gap is classified:
+//                      nothing / one D, I or R op / pure diagonal (see below; its mismatch mask stays in the joint) / a DP problem (sort key = strip width, rows);
+//                      the clump's exact-match end extensions and the two X-drop extension problems for k_ext_rows; the edit list (M ops + joint ops) of a
+//                      root without a DP joint -- the others go to a compact list
 //     [radix sort of the DP joints by size, so that the lanes of a wave run problems of the same shape]
 //     k_gap_lanes<GW>  lane per DP joint: gapDPLane (the sequential recurrence, strip state and both sequences in LDS)
 //     k_gap_wave       wave per DP joint for the few that exceed gapDPLane's limits (dp_wave.h)
-//     k_p1_assemble    lane per root: edit list = M ops + joint ops, the clump's exact-match end extensions, the two
-//                      X-drop extension problems for k_ext_rows
+//     k_p1_assemble    lane per root of the compact list: its edit list from the joint records and the gap-op arena
 //   phase 3 = the tail of extendClumpForwardReverse + scoreClump / splitClump (AlignExtFrag.cpp:112-141, AlignHelpers.c:302-579)
 //     k_p3_lanes       lane per root: merge the extension results, scoreClump; accepted clumps are written by their lane;
 //                      for a root that needs splitClump the careful extensions it will ask for are listed (predictCarefulDPs)
@@ -29,8 +30,10 @@
 struct RootState { uint32_t sro, listOff; int32_t score; uint16_t sqo, eqo, refLen, len; uint8_t status, pad[3]; uint32_t pad2[2]; };
 enum { JK_NONE = 0, JK_D, JK_I, JK_R, JK_DIAG, JK_DP };
 struct JointRec {                                           // 32 B
-    uint32_t nsro, qBase; uint16_t nsqo, qGap, rGap; uint8_t kind, flags;   // flags: bit0 strand, bit1 banded
-    uint32_t opsOff; uint16_t nOps, pad; int32_t score; uint32_t cells;
+    uint32_t nsro, qBase; uint16_t nsqo, qGap, rGap; uint8_t kind, flags;   // flags: bit0 strand, bit1 banded, bit2 JF_DIAG_LONG (a DIAG joint without a mask)
+    uint32_t opsOff; uint16_t nOps, pad; int32_t score; uint32_t cells;     // pad: the M length of the fragment in front of the joint (k_p1_roots)
+    // JK_DP: opsOff / nOps = its list in the gap-op arena, cells = the DP's cell count (the gap fills).  JK_DIAG of qGap <= 64: opsOff | cells << 32 = the mismatch
+    // mask, bit t = base t differs (k_p1_roots); nOps unused
 };
 struct PhaseArgs {
     RootState *state; uint32_t *stateOps; unsigned int *stateOpsCount; uint32_t stateOpsCap;
@@ -48,6 +51,7 @@ struct PhaseArgs {
     uint32_t *gapOps; unsigned int *gapOpsCount; uint32_t gapOpsCap;
     uint32_t *extKeys, *extVals;                        // k_ext_rows takes the problems longest-bound first (keys = 0xFFFF - qLen)
     uint8_t *gapScratch;                                // YD_GAP_SCRATCH bytes per k_gap_lanes thread (trace strip + op list of gapDPLane)
+    uint32_t *pendList; unsigned int *pendCount;        // the roots with a DP joint: k_p1_roots lists them, k_p1_assemble takes them after the gap fills
 };
 
 // ---- wave helpers ----
@@ -222,6 +226,7 @@ __global__ void k_joint_counts(AlignArgs A, PhaseArgs X)
 // byte loop had two dependent loads per base.  A window is only read when all eight positions are inside [0, maxLen): no access the byte loop would not make,
 // except the bytes that complete the reference window's 8-byte load (inside the image's slack).
 typedef unsigned long long yd_u64u __attribute__((aligned(1)));
+typedef uint32_t yd_u32x4u __attribute__((ext_vector_type(4), aligned(4)));
 template <int DIR>
 __device__ __forceinline__ int matchRun(YD_GLOBAL const uint8_t *q, int qi, YD_GLOBAL const uint8_t *gB, uint32_t ro, int maxLen)
 {
@@ -291,68 +296,254 @@ __device__ __forceinline__ uint32_t wgDeal(uint32_t root, uint32_t cls)
     return sOrder[threadIdx.x];
 }
 
-// lane per root: exact-match extensions of every joint (AlignHelpers.c:216-232), then the gap's kind (AlignExtFrag.cpp:190-231)
-__global__ void __launch_bounds__(256) k_p1_joints(AlignArgs A, PhaseArgs X)
+// A DIAG joint's mismatch mask: bit t = query base nsqo + t differs from reference base nsro + t, g <= 64.  Eight bases a step with matchRun's nibble folding (XOR of the two
+// nibble streams, one bit per non-zero nibble); the last g % 8 bases byte by byte.  Reads what the byte loop reads (and the bytes that complete a reference window, as matchRun).
+__device__ __forceinline__ unsigned long long diagMask(YD_GLOBAL const uint8_t *q, int qi, YD_GLOBAL const uint8_t *gB, uint32_t ro, int g)
+{
+    unsigned long long mask = 0; int t = 0;
+    for (; g - t >= 8; t += 8) {
+        unsigned long long qx = *(YD_GLOBAL const yd_u64u *)(q + qi + t);
+        qx = (qx | (qx >> 4)) & 0x00FF00FF00FF00FFull; qx = (qx | (qx >> 8)) & 0x0000FFFF0000FFFFull;
+        const uint32_t qs = (uint32_t)(qx | (qx >> 16)); const uint32_t ra = ro + (uint32_t)t;
+        unsigned long long rx = *(YD_GLOBAL const yd_u64u *)(gB + (ra >> 1));
+        rx = ((rx & 0x0F0F0F0F0F0F0F0Full) << 4) | ((rx >> 4) & 0x0F0F0F0F0F0F0F0Full);
+        uint32_t d = qs ^ (uint32_t)(rx >> (4u * (ra & 1u)));
+        d |= d >> 1; d |= d >> 2; d &= 0x11111111u;                              // bit 4i = nibble i differs
+        d = (d | (d >> 3)) & 0x03030303u; d = (d | (d >> 6)) & 0x000F000Fu; d = (d | (d >> 12)) & 0xFFu;
+        mask |= (unsigned long long)d << t;
+    }
+    for (; t < g; t++) { const uint32_t off = ro + (uint32_t)t, b = gB[off >> 1];
+        if ((uint32_t)q[qi + t] != ((off & 1u) ? (b & 15u) : (b >> 4))) mask |= 1ull << t; }
+    return mask;
+}
+
+// a root that waits for its gap fills: what k_p1_roots knows of it, kept in the root's RootState slot (32 B) until k_p1_assemble writes the state itself
+struct RootPend { uint32_t sro, jb; uint16_t sqo, eqo, refLen, lastM, firstAdd, forwAdd; uint32_t n; uint8_t status, pad[3]; uint32_t pad2; };
+static_assert(sizeof(RootPend) == sizeof(RootState), "RootPend lives in the RootState slot");
+#define JF_DIAG_LONG 4u                                  // JointRec::flags of a DIAG joint of more than 64 bases: no mask, its ops come from the sequences
+// A DP joint's op list inside its own record (JF_INLINE): at most YD_JINL ops, none longer than 64, one byte an op -- code : 2 | (len - 1) : 6 -- in list order in the
+// fields the finished DP leaves dead: bytes 0..7 = nsro | qBase << 32, 8..9 = nsqo, 10..13 = opsOff.  (pad keeps the fragment's M length; qGap, rGap, score, cells
+// are read by the assemble kernel.)  83 % of a bench batch's DP joints fit (profiles/p1_one_pass.txt): no arena slot, no line of the arena to fetch.  Longer
+// lists, lists with a longer op and k_gap_wave's joints go to the gap-op arena as before.
+#define JF_INLINE 8u
+#define YD_JINL 14
+__host__ __device__ __forceinline__ uint32_t jointInlineOp(const JointRec &j, int k)
+{
+    const uint32_t b = k < 8 ? (uint32_t)((((unsigned long long)j.qBase << 32) | j.nsro) >> (8 * k)) : (k < 10 ? (uint32_t)j.nsqo >> (8 * (k - 8)) : j.opsOff >> (8 * (k - 10)));
+    return ((b & 3u) << 16) | (((b >> 2) & 63u) + 1u);
+}
+// The tail of a lane gap-fill kernel: the list a lane holds (list element k = tmp[(nT - 1 - k) * 64]; have = the lane finished a joint) goes into the joint record
+// or, by wave prefix sum and one atomic a wave that has any, into the arena.  Every lane of the wave calls it.
+__device__ __forceinline__ void gapListOut(const AlignArgs &A, const PhaseArgs &X, int lane, bool have, uint32_t ji, const uint32_t *tmp, int nT, int score, unsigned cells)
+{
+    bool inl = have && nT <= YD_JINL; unsigned long long lo = 0; uint32_t mid = 0, hi = 0;
+    if (inl) for (int k = 0; k < nT; k++) {
+        const uint32_t op = tmp[(nT - 1 - k) * 64]; const uint32_t code = op >> 16; const int len = opLen(op);
+        if (code > 3u || len < 1 || len > 64) { inl = false; break; }
+        const uint32_t b = code | ((uint32_t)(len - 1) << 2);
+        if (k < 8) lo |= (unsigned long long)b << (8 * k); else if (k < 10) mid |= b << (8 * (k - 8)); else hi |= b << (8 * (k - 10));
+    }
+    const int nA = (have && !inl) ? nT : 0;
+    int incl = nA;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { int v = __shfl_up(incl, d, 64); if (lane >= d) incl += v; }
+    const int total = __shfl(incl, 63, 64); unsigned ob = 0;
+    if (lane == 63 && total) ob = atomicAdd(X.gapOpsCount, (unsigned)total);
+    ob = (unsigned)__shfl((int)ob, 63, 64);
+    if (!have) return;
+    JointRec *jp = X.joints + ji;
+    if (inl) {
+        jp->nsro = (uint32_t)lo; jp->qBase = (uint32_t)(lo >> 32); jp->nsqo = (uint16_t)mid; jp->opsOff = hi; jp->flags |= (uint8_t)JF_INLINE;
+        jp->nOps = (uint16_t)nT; jp->score = score; jp->cells = cells;
+        return;
+    }
+    const unsigned off = ob + (unsigned)(incl - nA);
+    if ((unsigned long long)off + (unsigned)nT > (unsigned long long)X.gapOpsCap) { atomicCAS(A.errFlag, 0, (int)YERR_OUT); return; }
+    for (int k = 0; k < nT; k++) X.gapOps[off + k] = tmp[(nT - 1 - k) * 64];    // list order
+    jp->opsOff = off; jp->nOps = (uint16_t)nT; jp->score = score; jp->cells = cells;
+}
+
+// The phase-1 edit list of one root from its joints: [M of fragment 0 + the backward end extension][joint 0][M of fragment 1] ... [M of the last fragment + the forward end
+// extension], equal neighbours merged (collapseSFragments).  A fragment's M length is in the joint behind it (JointRec::pad), the last one's in lastM; a DIAG joint's ops are
+// the runs of its mask; a DP joint's (WITH_DP: after the gap fills) come from the gap-op arena through a window of four.  Returns the list's length.
+template <bool WITH_DP>
+__device__ __forceinline__ int emitRootList(const AlignArgs &A, const PhaseArgs &X, uint32_t jb, int n, int firstAdd, int forwAdd, int lastM, uint32_t *ops, int &scoreOut,
+                                            unsigned &gapCells)
+{
+    const DevParams &P = A.P;
+    int nOut = 0, pc = OP_M, pl = firstAdd & 0xFFFF, score = (firstAdd + forwAdd) * P.MS;
+    auto put = [&](int code, int len) { if (pc == code) { pl = (pl + len) & 0xFFFF; return; } ops[nOut] = opMake(pc, pl); nOut++; pc = code; pl = len & 0xFFFF; };
+    for (int k = 0; k + 1 < n; k++) {
+        const JointRec j = X.joints[jb + (uint32_t)k]; const int qGap = j.qGap, rGap = j.rGap;
+        { const int ql = (int)j.pad; put(OP_M, ql); score += P.MS * ql; }
+        if (j.kind == JK_D) { put(OP_D, rGap); score -= P.GO + rGap * P.GE; }
+        else if (j.kind == JK_I) { put(OP_I, qGap); score -= P.GO + qGap * P.GE; }
+        else if (j.kind == JK_R) { put(OP_R, 1); score -= P.RC; }
+        else if (j.kind == JK_DIAG) {
+            const int g = qGap;
+            if (j.flags & JF_DIAG_LONG) {
+                YD_GLOBAL const uint8_t *q = toGlobal((j.flags & 1u) ? A.B.rev : A.B.fwd) + j.qBase; YD_GLOBAL const uint8_t *gB = toGlobal(A.bases);
+                for (int t = 0; t < g; t++) { const uint32_t off = j.nsro + (uint32_t)t, b = gB[off >> 1];
+                    put((uint32_t)q[(int)j.nsqo + t] == ((off & 1u) ? (b & 15u) : (b >> 4)) ? OP_M : OP_R, 1); }
+            } else {
+                const unsigned long long m = (unsigned long long)j.opsOff | ((unsigned long long)j.cells << 32);
+                for (int t = 0; t < g; ) {                                       // one put per run of equal bits
+                    const bool mis = ((m >> t) & 1ull) != 0; const unsigned long long x = (mis ? ~m : m) >> t;
+                    int run = x ? __builtin_ctzll(x) : 64; if (run > g - t) run = g - t;
+                    put(mis ? OP_R : OP_M, run); t += run;
+                }
+            }
+            score += j.score;
+        } else if (WITH_DP && j.kind == JK_DP) {
+            const uint32_t *seg = X.gapOps + j.opsOff; uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
+            if (j.flags & JF_INLINE) for (int t = 0; t < (int)j.nOps; t++) { const uint32_t op = jointInlineOp(j, t); put(opCode(op), opLen(op)); }
+            else for (int t = 0; t < (int)j.nOps; t++) {
+                if ((t & 3) == 0) { const yd_u32x4u v = *(YD_GLOBAL const yd_u32x4u *)toGlobal(seg + t); w0 = v.x; w1 = v.y; w2 = v.z; w3 = v.w; }
+                const int sl = t & 3; const uint32_t op = sl == 0 ? w0 : (sl == 1 ? w1 : (sl == 2 ? w2 : w3));
+                put(opCode(op), opLen(op));
+            }
+            score += j.score; gapCells += j.cells;
+        }
+    }
+    put(OP_M, lastM); score += P.MS * lastM;
+    pl = (pl + forwAdd) & 0xFFFF;
+    ops[nOut] = opMake(pc, pl); nOut++;
+    scoreOut = score;
+    return nOut;
+}
+
+// lane per root, every root: the exact-match extensions of every joint (AlignHelpers.c:216-232), the gap's kind (AlignExtFrag.cpp:190-231), the clump's exact-match end
+// extensions (AlignExtFrag.cpp:76-107) and the two X-drop extension problems -- none of which waits for a gap fill.  A root without a DP joint (one fragment, or joints of
+// one op or a pure diagonal only) is finished here: edit list and RootState.  The others leave a RootPend and go to the compact list that k_p1_assemble takes.
+// The fragments are not written back: the joint records carry what the list needs of them.
+__global__ void __launch_bounds__(256) k_p1_roots(AlignArgs A, PhaseArgs X)
 {
     YD_HIGH_PRIO();
     // (wgDeal by the number of fragments, measured: 1.64 -> 1.61 ms here, 2.39 -> 2.66 ms in k_p1_assemble -- their per-root records are written side by side by
     // neighbouring lanes -- and the step 0.2 ms slower: not used)
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = laneId(); const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = r < A.nRoots; const DevParams &P = A.P;
-    unsigned perfect = 0, touched = 0, nDP = 0, nDP16 = 0, nB12 = 0, nB16 = 0, nB24 = 0;
+    unsigned perfect = 0, touched = 0, gapCalls = 0, gapRows = 0, gapCells = 0, nDP = 0, nDP16 = 0, nB12 = 0, nB16 = 0, nB24 = 0;
+    unsigned want = 0; bool pend = false; uint32_t jb = 0, sro = 0; int n = 0, firstAdd = 0, forwAdd = 0, lastM = 0, sqo = 0, eqo = 0, refLen = 0; uint8_t status = 0;
     if (live) {
-        const ChainClumpRec rec = YD_ROOT_REC(A, r); const int n = (int)rec.nFrags;
-        if (n > 1) {
-            const uint32_t read = rec.rs >> 1, r0 = A.B.readOff[read];
-            YD_GLOBAL const uint8_t *q = toGlobal((rec.rs & 1u) ? A.B.rev : A.B.fwd) + r0; YD_GLOBAL const uint8_t *gB = toGlobal(A.bases);
-            auto refAt = [&](uint32_t off) -> uint32_t { const uint32_t b = gB[off >> 1]; return (off & 1u) ? (b & 15u) : (b >> 4); };
-            DevFrag *F = A.clumpFrags + rec.fragOff; const uint32_t jb = X.jointBase[r];
-            DevFrag cur = F[0];
-            for (int k = 1; k < n; k++) {
-                DevFrag nxt = F[k];
-                int gap = (int)min(gapI(cur.eqo, nxt.sqo), gapU(cur.sro + (uint32_t)cur.refLen - 1u, nxt.sro));
-                { const int c = matchRun<-1>(q, (int)nxt.sqo - 1, gB, nxt.sro - 1u, gap);
-                  perfect += c; touched += c + (c < gap);
-                  if (c > 0) { nxt.sqo = (uint16_t)(nxt.sqo - c); nxt.sro -= (uint32_t)c; nxt.refLen = (uint16_t)(nxt.refLen + c); } gap -= c; }
-                { const uint32_t eRO = cur.sro + (uint32_t)cur.refLen - 1u; const int c = matchRun<1>(q, (int)cur.eqo + 1, gB, eRO + 1u, gap);
-                  perfect += c; touched += c + (c < gap);
-                  if (c > 0) { cur.eqo = (uint16_t)(cur.eqo + c); cur.refLen = (uint16_t)(cur.refLen + c); } }
-                F[k - 1] = cur;
-                const uint32_t eRO = cur.sro + (uint32_t)cur.refLen - 1u;
-                const int qGap = (int)(gapI(cur.eqo, nxt.sqo) & 0xFFFF), rGap = (int)(gapU(eRO, nxt.sro) & 0xFFFF);
-                JointRec j; j.nsro = eRO + 1u; j.qBase = r0; j.nsqo = (uint16_t)((cur.eqo + 1) & 0xFFFF); j.qGap = (uint16_t)qGap; j.rGap = (uint16_t)rGap;
-                j.flags = (uint8_t)(rec.rs & 1u); j.opsOff = 0; j.nOps = 0; j.pad = 0; j.score = 0; j.cells = 0; j.kind = JK_NONE;
-                uint32_t key = YD_JKEY_NONE;
-                if (qGap == 0 && rGap == 0) { }
-                else if (qGap == 0) j.kind = JK_D;
-                else if (rGap == 0) j.kind = JK_I;
-                else if (rGap == 1 && qGap == 1) j.kind = JK_R;
-                else {
-                    const int lenDiff = qGap > rGap ? qGap - rGap : rGap - qGap;
-                    const bool banded = lenDiff + P.bandWidth * 2 + 1 < rGap;
-                    j.flags |= banded ? 2u : 0u; j.kind = JK_DP;
-                    if (qGap == rGap) {
-                        int mm = 0;
-                        for (int t = 0; t < qGap; t++) mm += (uint32_t)q[(int)cur.eqo + 1 + t] != refAt(eRO + 1u + (uint32_t)t);
-                        if (mm * (P.MS + P.RC) <= P.MS + 2 * (P.GO + P.GE)) { j.kind = JK_DIAG; j.score = P.MS * (qGap - mm) - P.RC * mm; }
+        const ChainClumpRec rec = YD_ROOT_REC(A, r); n = (int)rec.nFrags;
+        const uint32_t read = rec.rs >> 1, r0 = A.B.readOff[read]; const int qlen = (int)(A.B.readOff[read + 1] - r0);
+        YD_GLOBAL const uint8_t *q = toGlobal((rec.rs & 1u) ? A.B.rev : A.B.fwd) + r0; YD_GLOBAL const uint8_t *gB = toGlobal(A.bases);
+        const DevFrag *F = A.clumpFrags + rec.fragOff; jb = X.jointBase[r];
+        const DevFrag firstF = F[0]; DevFrag cur = firstF;
+        want = (unsigned)n + 1u;                                                 // exact upper bound of the list length (of a root that is finished here)
+        for (int k = 1; k < n; k++) {
+            DevFrag nxt = F[k];
+            int gap = (int)min(gapI(cur.eqo, nxt.sqo), gapU(cur.sro + (uint32_t)cur.refLen - 1u, nxt.sro));
+            { const int c = matchRun<-1>(q, (int)nxt.sqo - 1, gB, nxt.sro - 1u, gap);
+              perfect += c; touched += c + (c < gap);
+              if (c > 0) { nxt.sqo = (uint16_t)(nxt.sqo - c); nxt.sro -= (uint32_t)c; nxt.refLen = (uint16_t)(nxt.refLen + c); } gap -= c; }
+            { const uint32_t eRO = cur.sro + (uint32_t)cur.refLen - 1u; const int c = matchRun<1>(q, (int)cur.eqo + 1, gB, eRO + 1u, gap);
+              perfect += c; touched += c + (c < gap);
+              if (c > 0) { cur.eqo = (uint16_t)(cur.eqo + c); cur.refLen = (uint16_t)(cur.refLen + c); } }
+            const uint32_t eRO = cur.sro + (uint32_t)cur.refLen - 1u;
+            const int qGap = (int)(gapI(cur.eqo, nxt.sqo) & 0xFFFF), rGap = (int)(gapU(eRO, nxt.sro) & 0xFFFF);
+            JointRec j; j.nsro = eRO + 1u; j.qBase = r0; j.nsqo = (uint16_t)((cur.eqo + 1) & 0xFFFF); j.qGap = (uint16_t)qGap; j.rGap = (uint16_t)rGap;
+            j.flags = (uint8_t)(rec.rs & 1u); j.opsOff = 0; j.nOps = 0; j.pad = (uint16_t)fragQLen(cur.sqo, cur.eqo); j.score = 0; j.cells = 0; j.kind = JK_NONE;
+            uint32_t key = YD_JKEY_NONE;
+            if (qGap == 0 && rGap == 0) { }
+            else if (qGap == 0) { j.kind = JK_D; want++; }
+            else if (rGap == 0) { j.kind = JK_I; want++; }
+            else if (rGap == 1 && qGap == 1) { j.kind = JK_R; want++; }
+            else {
+                const int lenDiff = qGap > rGap ? qGap - rGap : rGap - qGap;
+                const bool banded = lenDiff + P.bandWidth * 2 + 1 < rGap;
+                j.flags |= banded ? 2u : 0u; j.kind = JK_DP;
+                if (qGap == rGap) {
+                    const int g = qGap; int mm = 0; unsigned long long mask = 0;
+                    if (g <= 64) { mask = diagMask(q, (int)cur.eqo + 1, gB, eRO + 1u, g); mm = __builtin_popcountll(mask); }
+                    else for (int t = 0; t < g; t++) { const uint32_t off = eRO + 1u + (uint32_t)t, b = gB[off >> 1];
+                        mm += (uint32_t)q[(int)cur.eqo + 1 + t] != ((off & 1u) ? (b & 15u) : (b >> 4)); }
+                    if (mm * (P.MS + P.RC) <= P.MS + 2 * (P.GO + P.GE)) {
+                        j.kind = JK_DIAG; j.score = P.MS * (g - mm) - P.RC * mm;
+                        if (g <= 64) { j.opsOff = (uint32_t)mask; j.cells = (uint32_t)(mask >> 32); } else j.flags |= JF_DIAG_LONG;
+                        want += (unsigned)g; gapCalls++; gapRows += (unsigned)g; touched += (unsigned)g;      // charged as the reference's DP would have counted them
+                        if (P.bandWidth * 2 + 1 < g) { const int bw = P.bandWidth, W = 2 * bw + 1; for (int i = 1; i <= g; i++) { int sc = bw + 1 - i; if (sc < 0) sc = 0;
+                            int ec = bw + g - i; if (ec > W - 1) ec = W - 1; if (ec >= sc) gapCells += (unsigned)(ec - sc + 1); } }
+                        else gapCells += (unsigned)(g * g);
                     }
-                    if (j.kind == JK_DP) { key = gapJointKey(P, banded, qGap, rGap); const uint32_t cls = gapJointClass(key); nDP++; nDP16 += cls <= 2u; nB12 += cls == 0u;
-                        nB16 += cls <= 1u; nB24 += gapJointBand24(key) ? 1u : 0u; }
                 }
-                X.joints[jb + (uint32_t)(k - 1)] = j; X.sortKeys[jb + (uint32_t)(k - 1)] = key; X.sortVals[jb + (uint32_t)(k - 1)] = jb + (uint32_t)(k - 1);
-                cur = nxt;
+                if (j.kind == JK_DP) { key = gapJointKey(P, banded, qGap, rGap); const uint32_t cls = gapJointClass(key); nDP++; nDP16 += cls <= 2u; nB12 += cls == 0u;
+                    nB16 += cls <= 1u; nB24 += gapJointBand24(key) ? 1u : 0u;
+                    pend = true; gapCalls++; gapRows += (unsigned)qGap; touched += (unsigned)rGap; }          // (its cells: k_p1_assemble)
             }
-            F[n - 1] = cur;
+            X.joints[jb + (uint32_t)(k - 1)] = j; X.sortKeys[jb + (uint32_t)(k - 1)] = key; X.sortVals[jb + (uint32_t)(k - 1)] = jb + (uint32_t)(k - 1);
+            cur = nxt;
+        }
+        lastM = fragQLen(cur.sqo, cur.eqo);
+        // the clump's fragment and its exact-match end extensions
+        sro = firstF.sro; sqo = firstF.sqo; eqo = cur.eqo; refLen = (int)((1u + (cur.sro + (uint32_t)cur.refLen - 1u) - firstF.sro) & 0xFFFFu);
+        int backLen = (int)((uint32_t)sqo < sro ? (uint32_t)sqo : sro), forwLen;
+        if (backLen > 0) {
+            const int m = matchRun<-1>(q, sqo - 1, gB, sro - 1u, backLen);
+            perfect += m; touched += m + (m < backLen);
+            if (m > 0) { firstAdd = m; backLen -= m; sqo -= m; sro -= (uint32_t)m; refLen = (refLen + m) & 0xFFFF; }
+        }
+        {
+            const uint32_t eRO = sro + (uint32_t)refLen - 1u;
+            const uint32_t qrem = (uint32_t)(((qlen - 1) - eqo) & 0xFFFF), rrem = P.maxROff - eRO;
+            forwLen = (int)(qrem < rrem ? qrem : rrem);
+            if (forwLen > 0) {
+                const int m = matchRun<1>(q, eqo + 1, gB, eRO + 1u, forwLen);
+                perfect += m; touched += m + (m < forwLen);
+                if (m > 0) { forwAdd = m; forwLen -= m; eqo += m; refLen = (refLen + m) & 0xFFFF; }
+            }
+        }
+        status = (rec.rs & 1u) ? stReversed : 0;
+        const uint32_t strand = (rec.rs & 1u) ? XP_STRAND : 0u; const bool vb = backLen >= P.minExtLength, vf = forwLen >= P.minExtLength;
+        ExtProb pb; pb.qBase = r0; pb.rOff = sro - 1u; pb.qOff = (uint16_t)((sqo - 1) & 0xFFFF); pb.qLen = (uint16_t)(backLen & 0xFFFF);
+            pb.flags = strand | XP_REV | (vb ? XP_VALID : 0u);
+        ExtProb pf; pf.qBase = r0; pf.rOff = sro + (uint32_t)refLen; pf.qOff = (uint16_t)((eqo + 1) & 0xFFFF); pf.qLen = (uint16_t)(forwLen & 0xFFFF);
+            pf.flags = strand | (vf ? XP_VALID : 0u);
+        X.probs[2 * (size_t)r] = pb; X.probs[2 * (size_t)r + 1] = pf;
+        // 16 bits: two radix passes (a valid problem has qLen >= 1)
+        X.extKeys[2 * (size_t)r] = vb ? 0xFFFFu - pb.qLen : 0xFFFFu; X.extKeys[2 * (size_t)r + 1] = vf ? 0xFFFFu - pf.qLen : 0xFFFFu;
+        X.extVals[2 * (size_t)r] = 2u * r; X.extVals[2 * (size_t)r + 1] = 2u * r + 1u;
+        // trace blocks of 10 rows: up to 9 rows of phase in front, one spare row behind
+        X.rowsBound[2 * (size_t)r] = vb ? (unsigned long long)((pb.qLen + 19u) / 10u) : 0ull;
+            X.rowsBound[2 * (size_t)r + 1] = vf ? (unsigned long long)((pf.qLen + 19u) / 10u) : 0ull;
+        if (pend) {
+            RootPend s; memset(&s, 0, sizeof s);
+            s.sro = sro; s.jb = jb; s.sqo = (uint16_t)sqo; s.eqo = (uint16_t)eqo; s.refLen = (uint16_t)refLen; s.lastM = (uint16_t)lastM; s.firstAdd = (uint16_t)firstAdd;
+                s.forwAdd = (uint16_t)forwAdd; s.n = (uint32_t)n; s.status = status;
+            *(RootPend *)(X.state + r) = s;
         }
     }
-    perfect = waveSumU(perfect); touched = waveSumU(touched); nDP = waveSumU(nDP); nDP16 = waveSumU(nDP16); nB12 = waveSumU(nB12); nB16 = waveSumU(nB16); nB24 = waveSumU(nB24);
-    { unsigned long long *const dst[2] = {&A.ctr->v[C_PERFECT], &A.ctr->v[C_TOUCHED]}; const unsigned val[2] = {perfect, touched}; blockCounters<2>(dst, val); }
+    // the roots that wait: a compact list, one reservation a wave
+    { const unsigned long long pm = __ballot(pend); const unsigned pi = waveReserve(pm, X.pendCount, lane); if (pend) X.pendList[pi] = r; }
+    // the others: list slots by wave prefix sum, one reservation a workgroup
+    const bool fin = live && !pend; if (!fin) want = 0;
+    unsigned incl = want;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { unsigned t = (unsigned)__shfl_up((int)incl, d, 64); if (lane >= d) incl += t; }
+    const unsigned total = (unsigned)__shfl((int)incl, 63, 64);
+    const unsigned base = blockReserve(X.stateOpsCount, total);
+    const unsigned slot = base + incl - want;
+    if (fin) {
+        if ((unsigned long long)slot + want > (unsigned long long)X.stateOpsCap) atomicCAS(A.errFlag, 0, (int)YERR_OUT);
+        else {
+            int score = 0; unsigned dpCells = 0;
+            const int nOut = emitRootList<false>(A, X, jb, n, firstAdd, forwAdd, lastM, X.stateOps + slot, score, dpCells);
+            RootState s; memset(&s, 0, sizeof s);
+            s.sro = sro; s.sqo = (uint16_t)sqo; s.eqo = (uint16_t)eqo; s.refLen = (uint16_t)refLen; s.score = score; s.status = status; s.len = (uint16_t)nOut; s.listOff = slot;
+            X.state[r] = s;
+        }
+    }
+    perfect = waveSumU(perfect); touched = waveSumU(touched); gapCalls = waveSumU(gapCalls); gapRows = waveSumU(gapRows); gapCells = waveSumU(gapCells);
+    nDP = waveSumU(nDP); nDP16 = waveSumU(nDP16); nB12 = waveSumU(nB12); nB16 = waveSumU(nB16); nB24 = waveSumU(nB24);
+    { unsigned long long *c = A.ctr->v; unsigned long long *const dst[5] = {&c[C_PERFECT], &c[C_TOUCHED], &c[C_GAP_CALLS], &c[C_GAP_ROWS], &c[C_GAP_CELLS]};
+      const unsigned val[5] = {perfect, touched, gapCalls, gapRows, gapCells}; blockCounters<5>(dst, val); }
     { unsigned int *const dst[5] = {X.nDP, X.nDP + 1, X.nDPb, X.nDPb + 1, X.nDPb + 2}; const unsigned val[5] = {nDP, nDP16, nB12, nB16, nB24}; blockCountersU32<5>(dst, val); }
 }
 
 // lane per DP joint, in size order (key = class, strip width, rows).  Persistent 64-thread blocks.  The sorted joints are [0, nB12) banded with W <= 12 and
 // [nB12, nB16) banded with W <= 16: k_gap_band<12|16> (gap_band_lanes.h);  [nB16, n16) the other W <= 16: the GW = 16 instance of this kernel;  [n16, nDP): GW = 32
-// (X.nDP[0] = nDP, X.nDP[1] = n16, X.nDPb[0] = nB12, X.nDPb[1] = nB16, counted by k_p1_joints); with X.band24 the first X.nDPb[2] joints of [n16, nDP) -- banded, W <= 24 --
+// (X.nDP[0] = nDP, X.nDP[1] = n16, X.nDPb[0] = nB12, X.nDPb[1] = nB16, counted by k_p1_roots); with X.band24 the first X.nDPb[2] joints of [n16, nDP) -- banded, W <= 24 --
 // are k_gap_band_pk<24>'s (gap_band_pk.h) and GW = 32 starts behind them.
 template <int GW>
 __global__ void __launch_bounds__(64) k_gap_lanes(AlignArgs A, PhaseArgs X)
@@ -381,21 +572,7 @@ __global__ void __launch_bounds__(64) k_gap_lanes(AlignArgs A, PhaseArgs X)
             }
         }
         { const unsigned long long mm = __ballot(tooBig); const unsigned sl = waveReserve(mm, X.slowCount, lane); if (tooBig) X.slowList[sl] = ji; }
-        // op slots: wave prefix sum of nT
-        int incl = nT;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { int v = __shfl_up(incl, d, 64); if (lane >= d) incl += v; }
-        const int total = __shfl(incl, 63, 64); unsigned ob = 0;
-        if (lane == 63 && total) ob = atomicAdd(X.gapOpsCount, (unsigned)total);
-        ob = (unsigned)__shfl((int)ob, 63, 64);
-        if (live && !tooBig) {
-            const unsigned off = ob + (unsigned)(incl - nT);
-            if ((unsigned long long)off + (unsigned)nT > (unsigned long long)X.gapOpsCap) atomicCAS(A.errFlag, 0, (int)YERR_OUT);
-            else {
-                for (int k = 0; k < nT; k++) X.gapOps[off + k] = GM.tmp[(nT - 1 - k) * 64];    // list order
-                JointRec *jp = X.joints + ji; jp->opsOff = off; jp->nOps = (uint16_t)nT; jp->score = score; jp->cells = cells;
-            }
-        }
+        gapListOut(A, X, lane, live && !tooBig, ji, GM.tmp, nT, score, cells);
     }
 }
 
@@ -426,101 +603,41 @@ __global__ void __launch_bounds__(64) k_gap_wave(AlignArgs A, PhaseArgs X)
     }
 }
 
-// lane per root: the edit list, the clump's fragment, its exact-match end extensions (AlignExtFrag.cpp:76-107), the
-// two X-drop extension problems
+// lane per root of the compact list (the roots with a DP joint), after the gap fills: the edit list from the joints and the RootPend k_p1_roots left, the RootState over
+// it.  Reads neither the fragments, the reads nor the genome (but for a DIAG joint of more than 64 bases).
 __global__ void __launch_bounds__(256) k_p1_assemble(AlignArgs A, PhaseArgs X)
 {
     YD_HIGH_PRIO();
-    const int lane = laneId(); const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = r < A.nRoots; const DevParams &P = A.P;
-    ChainClumpRec rec; rec.nFrags = 0; rec.rs = 0; rec.fragOff = 0;
-    if (live) rec = YD_ROOT_REC(A, r);
-    const int n = (int)rec.nFrags; const uint32_t jb = live ? X.jointBase[r] : 0u;
+    const int lane = laneId(); const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t nPend = *X.pendCount;
+    if (blockIdx.x * blockDim.x >= nPend) return;                               // (the grid is sized for the bound; the whole workgroup leaves)
+    const bool live = t < nPend;
+    uint32_t r = 0; RootPend S; memset(&S, 0, sizeof S);
+    if (live) { r = X.pendList[t]; S = *(const RootPend *)(X.state + r); }
+    const int n = (int)S.n; const uint32_t jb = S.jb;
     // exact upper bound of the list length
     unsigned want = 0;
     if (live) { want = (unsigned)n + 1u; for (int k = 0; k + 1 < n; k++) { const JointRec &j = X.joints[jb + (uint32_t)k];
         want += j.kind == JK_DP ? (unsigned)j.nOps : (j.kind == JK_DIAG ? (unsigned)j.qGap : (j.kind != JK_NONE ? 1u : 0u)); } }
     unsigned incl = want;
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { unsigned t = (unsigned)__shfl_up((int)incl, d, 64); if (lane >= d) incl += t; }
+    for (int d = 1; d < 64; d <<= 1) { unsigned v = (unsigned)__shfl_up((int)incl, d, 64); if (lane >= d) incl += v; }
     const unsigned total = (unsigned)__shfl((int)incl, 63, 64);
     const unsigned base = blockReserve(X.stateOpsCount, total);
     const unsigned slot = base + incl - want;
-    unsigned perfect = 0, touched = 0, gapCalls = 0, gapRows = 0, gapCells = 0;
+    unsigned gapCells = 0;
     if (live) {
         if ((unsigned long long)slot + want > (unsigned long long)X.stateOpsCap) atomicCAS(A.errFlag, 0, (int)YERR_OUT);
         else {
-            const uint32_t read = rec.rs >> 1, r0 = A.B.readOff[read]; const int qlen = (int)(A.B.readOff[read + 1] - r0);
-            YD_GLOBAL const uint8_t *q = toGlobal((rec.rs & 1u) ? A.B.rev : A.B.fwd) + r0; YD_GLOBAL const uint8_t *gB = toGlobal(A.bases);
-            auto refAt = [&](uint32_t off) -> uint32_t { const uint32_t b = gB[off >> 1]; return (off & 1u) ? (b & 15u) : (b >> 4); };
-            const DevFrag *F = A.clumpFrags + rec.fragOff;
-            uint32_t *ops = X.stateOps + slot; int nOut = 0, pc = -1, pl = 0, score = 0;
-            auto put = [&](int code, int len) { if (pc == code) { pl = (pl + len) & 0xFFFF; return; } if (pc >= 0) { ops[nOut] = opMake(pc, pl); nOut++; } pc = code;
-                pl = len & 0xFFFF; };
-            const DevFrag firstF = F[0]; DevFrag cur = firstF;
-            for (int k = 1; k <= n; k++) {
-                { const int ql = fragQLen(cur.sqo, cur.eqo); put(OP_M, ql); score += P.MS * ql; }
-                if (k == n) break;
-                const JointRec j = X.joints[jb + (uint32_t)(k - 1)]; const int qGap = j.qGap, rGap = j.rGap;
-                if (j.kind == JK_D) { put(OP_D, rGap); score -= P.GO + rGap * P.GE; }
-                else if (j.kind == JK_I) { put(OP_I, qGap); score -= P.GO + qGap * P.GE; }
-                else if (j.kind == JK_R) { put(OP_R, 1); score -= P.RC; }
-                else if (j.kind == JK_DIAG) {
-                    const int g = qGap;
-                    for (int t = 0; t < g; t++) put((uint32_t)q[(int)j.nsqo + t] == refAt(j.nsro + (uint32_t)t) ? OP_M : OP_R, 1);
-                    score += j.score; gapCalls++; gapRows += (unsigned)g; touched += (unsigned)g;
-                    if (P.bandWidth * 2 + 1 < g) { const int bw = P.bandWidth, W = 2 * bw + 1; for (int i = 1; i <= g; i++) { int sc = bw + 1 - i; if (sc < 0) sc = 0;
-                        int ec = bw + g - i; if (ec > W - 1) ec = W - 1; if (ec >= sc) gapCells += (unsigned)(ec - sc + 1); } }
-                    else gapCells += (unsigned)(g * g);
-                } else if (j.kind == JK_DP) {
-                    for (int t = 0; t < (int)j.nOps; t++) { const uint32_t op = X.gapOps[j.opsOff + (uint32_t)t]; put(opCode(op), opLen(op)); }
-                    score += j.score; gapCalls++; gapRows += (unsigned)qGap; gapCells += j.cells; touched += (unsigned)rGap;
-                }
-                cur = F[k];
-            }
-            uint32_t sro = firstF.sro; int sqo = firstF.sqo, eqo = cur.eqo; int refLen = (int)((1u + (cur.sro + (uint32_t)cur.refLen - 1u) - firstF.sro) & 0xFFFFu);
-            int firstAdd = 0;
-            int backLen = (int)((uint32_t)sqo < sro ? (uint32_t)sqo : sro), forwLen;
-            if (backLen > 0) {
-                const int m = matchRun<-1>(q, sqo - 1, gB, sro - 1u, backLen);
-                perfect += m; touched += m + (m < backLen);
-                if (m > 0) { firstAdd = m; score += m * P.MS; backLen -= m; sqo -= m; sro -= (uint32_t)m; refLen = (refLen + m) & 0xFFFF; }
-            }
-            {
-                const uint32_t eRO = sro + (uint32_t)refLen - 1u;
-                const uint32_t qrem = (uint32_t)(((qlen - 1) - eqo) & 0xFFFF), rrem = P.maxROff - eRO;
-                forwLen = (int)(qrem < rrem ? qrem : rrem);
-                if (forwLen > 0) {
-                    const int m = matchRun<1>(q, eqo + 1, gB, eRO + 1u, forwLen);
-                    perfect += m; touched += m + (m < forwLen);
-                    if (m > 0) { pl = (pl + m) & 0xFFFF; score += m * P.MS; forwLen -= m; eqo += m; refLen = (refLen + m) & 0xFFFF; }
-                }
-            }
-            if (nOut == 0) pl = (pl + firstAdd) & 0xFFFF;
-            ops[nOut] = opMake(pc, pl); nOut++;
-            if (nOut > 1 && firstAdd) ops[0] = opMake(opCode(ops[0]), (opLen(ops[0]) + firstAdd) & 0xFFFF);
+            int score = 0;
+            const int nOut = emitRootList<true>(A, X, jb, n, (int)S.firstAdd, (int)S.forwAdd, (int)S.lastM, X.stateOps + slot, score, gapCells);
             RootState s; memset(&s, 0, sizeof s);
-            s.sro = sro; s.sqo = (uint16_t)sqo; s.eqo = (uint16_t)eqo; s.refLen = (uint16_t)refLen; s.score = score; s.status = (rec.rs & 1u) ? stReversed : 0;
-                s.len = (uint16_t)nOut;
-            s.listOff = slot;
+            s.sro = S.sro; s.sqo = S.sqo; s.eqo = S.eqo; s.refLen = S.refLen; s.score = score; s.status = S.status; s.len = (uint16_t)nOut; s.listOff = slot;
             X.state[r] = s;
-            const uint32_t strand = (rec.rs & 1u) ? XP_STRAND : 0u; const bool vb = backLen >= P.minExtLength, vf = forwLen >= P.minExtLength;
-            ExtProb pb; pb.qBase = r0; pb.rOff = sro - 1u; pb.qOff = (uint16_t)((sqo - 1) & 0xFFFF); pb.qLen = (uint16_t)(backLen & 0xFFFF);
-                pb.flags = strand | XP_REV | (vb ? XP_VALID : 0u);
-            ExtProb pf; pf.qBase = r0; pf.rOff = sro + (uint32_t)refLen; pf.qOff = (uint16_t)((eqo + 1) & 0xFFFF); pf.qLen = (uint16_t)(forwLen & 0xFFFF);
-                pf.flags = strand | (vf ? XP_VALID : 0u);
-            X.probs[2 * (size_t)r] = pb; X.probs[2 * (size_t)r + 1] = pf;
-            // 16 bits: two radix passes (a valid problem has qLen >= 1)
-            X.extKeys[2 * (size_t)r] = vb ? 0xFFFFu - pb.qLen : 0xFFFFu; X.extKeys[2 * (size_t)r + 1] = vf ? 0xFFFFu - pf.qLen : 0xFFFFu;
-            X.extVals[2 * (size_t)r] = 2u * r; X.extVals[2 * (size_t)r + 1] = 2u * r + 1u;
-            // trace blocks of 10 rows: up to 9 rows of phase in front, one spare row behind
-            X.rowsBound[2 * (size_t)r] = vb ? (unsigned long long)((pb.qLen + 19u) / 10u) : 0ull;
-                X.rowsBound[2 * (size_t)r + 1] = vf ? (unsigned long long)((pf.qLen + 19u) / 10u) : 0ull;
         }
     }
-    perfect = waveSumU(perfect); touched = waveSumU(touched); gapCalls = waveSumU(gapCalls); gapRows = waveSumU(gapRows); gapCells = waveSumU(gapCells);
-    { unsigned long long *c = A.ctr->v; unsigned long long *const dst[5] = {&c[C_PERFECT], &c[C_TOUCHED], &c[C_GAP_CALLS], &c[C_GAP_ROWS], &c[C_GAP_CELLS]};
-      const unsigned val[5] = {perfect, touched, gapCalls, gapRows, gapCells}; blockCounters<5>(dst, val); }
+    gapCells = waveSumU(gapCells);
+    { unsigned long long *const dst[1] = {&A.ctr->v[C_GAP_CELLS]}; const unsigned val[1] = {gapCells}; blockCounters<1>(dst, val); }
 }
 
 // Phase 3 for roots that scoreClump accepts or rejects without a split (AlignHelpers.c:302-366): the merged edit list
@@ -531,7 +648,6 @@ __global__ void __launch_bounds__(256) k_p1_assemble(AlignArgs A, PhaseArgs X)
 __device__ __forceinline__ int opScore(const DevParams &P, int code, int len) { return len * (code == OP_M ? P.MS : (code == OP_R ? -P.RC : -P.GE)) + (code >= OP_D ? -P.GO : 0); }
 #define YD_OP_COUNT(code, len, m, r, i, d) \
     do { m += (code) == OP_M ? (len) : 0; r += (code) == OP_R ? (len) : 0; i += (code) == OP_I ? (len) : 0; d += (code) == OP_D ? (len) : 0; } while (0)
-typedef uint32_t yd_u32x4u __attribute__((ext_vector_type(4), aligned(4)));
 struct MergedOps {
     const uint32_t *a, *b, *c; int na, nb, nc; int jab, jbc;      // junction merges (mergeEOLToFront / mergeEOLToBack, SW.cpp:151-261)
     // a = the backward extension's ops as k_ext_trace leaves them (list order reversed): list element k = a[na-1-k]

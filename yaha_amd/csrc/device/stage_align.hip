@@ -135,7 +135,8 @@ struct LanePass {
     AlignArgs Ac; PhaseArgs Xc, Xw; uint32_t cap2 = 0, nSlow = 0, n2 = 0;    // its arguments (Xw: k_align_p3's), split roots, careful extensions listed
 };
 
-// phase 1: the joints of all roots -> gap fills -> k_p1_assemble (phase-1 lists, the extension problems and their row bounds) -> scan of the bounds
+// phase 1: k_p1_roots (joints, extension problems and their row bounds of all roots; the lists of the roots without a DP joint) -> gap fills -> k_p1_assemble (the lists
+// of the other roots) -> scan of the bounds
 static int phase1(ygpu_ctx *ctx, LanePass &L, uint32_t stateOpsCap, uint32_t gapOpsPerJoint)
 {
     const uint32_t NC = L.NC, nProb = L.nProb; uint32_t *cnt = L.cnt; const AlignArgs &A = L.A; PhaseArgs &X = L.X; int rc;
@@ -161,21 +162,24 @@ static int phase1(ygpu_ctx *ctx, LanePass &L, uint32_t stateOpsCap, uint32_t gap
     const uint32_t gapOpsCap = (uint32_t)std::min<uint64_t>(0x7FFFFFF0ull, (uint64_t)gapOpsPerJoint * J + (1u << 20));
     ENSURE(ctx->joints, sizeof(JointRec) * (uint64_t)(J + 1)); ENSURE(ctx->sortKeys, 4ull * (J + 1)); ENSURE(ctx->sortVals, 4ull * (J + 1)); ENSURE(ctx->sortKeys2, 4ull * (J + 1));
         ENSURE(ctx->sortVals2, 4ull * (J + 1));
-    ENSURE(ctx->gapOps, 4ull * gapOpsCap); ENSURE(ctx->slowList, 4ull * (std::max(NC, J) + 1));
+    ENSURE(ctx->gapOps, 4ull * gapOpsCap + 16); ENSURE(ctx->slowList, 4ull * (std::max(NC, J) + 1));
     X.slowList = ctx->slowList.as<uint32_t>();
     X.joints = ctx->joints.as<JointRec>(); X.nJoints = J; X.sortKeys = ctx->sortKeys.as<uint32_t>(); X.sortVals = ctx->sortVals.as<uint32_t>();
         X.sortedVals = ctx->sortVals2.as<uint32_t>();
     X.nDP = cnt + CNT_NDP; X.nDPb = cnt + CNT_NB12; X.gapOps = ctx->gapOps.as<uint32_t>(); X.gapOpsCount = cnt + CNT_GAPOPS; X.gapOpsCap = gapOpsCap;
-    HIPCHK(hipMemsetAsync(cnt + CNT_NDP, 0, 12, ctx->stream)); HIPCHK(hipMemsetAsync(cnt + CNT_NB12, 0, 12, ctx->stream));      // ndp, ndp16, gapops; nb12, nb16, nb24
+    HIPCHK(hipMemsetAsync(cnt + CNT_NDP, 0, 16, ctx->stream)); HIPCHK(hipMemsetAsync(cnt + CNT_NB12, 0, 12, ctx->stream));      // ndp, ndp16, gapops, npend; nb12, nb16, nb24
+    ENSURE(ctx->extKeys, 4ull * (nProb + 1)); ENSURE(ctx->extVals, 4ull * (nProb + 1)); ENSURE(ctx->extKeys2, 4ull * (nProb + 1)); ENSURE(ctx->extOrder, 4ull * (nProb + 1));
+    X.extKeys = ctx->extKeys.as<uint32_t>(); X.extVals = ctx->extVals.as<uint32_t>();
+    ENSURE(ctx->pendList, 4ull * (NC + 1)); X.pendList = ctx->pendList.as<uint32_t>(); X.pendCount = cnt + CNT_NPEND;
+    // every root: joints, end extensions, extension problems; the roots without a DP joint are finished by it
+    KL(k_p1_roots, dim3(gridFor(NC, 256)), dim3(256), 0, ctx->stream, A, X);
     if (J) {
-        KL(k_p1_joints, dim3(gridFor(NC, 256)), dim3(256), 0, ctx->stream, A, X);
         // joints of one (class, width, rows / 2) together
         rc = bucketOrder(ctx, X.sortKeys, X.sortVals, 0, J, 0, 0, 1u << YD_JKEY_BITS, ctx->sortVals2.as<uint32_t>(), ctx->stream); if (rc) return rc;
         rc = launchGapFills(ctx, A, X, J, std::min(L.waves, 512u)); if (rc) return rc;
+        // the roots that waited for a gap fill (at most one a joint; the workgroups beyond their count leave at once)
+        KL(k_p1_assemble, dim3(gridFor(std::min(NC, J), 256)), dim3(256), 0, ctx->stream, A, X);
     }
-    ENSURE(ctx->extKeys, 4ull * (nProb + 1)); ENSURE(ctx->extVals, 4ull * (nProb + 1)); ENSURE(ctx->extKeys2, 4ull * (nProb + 1)); ENSURE(ctx->extOrder, 4ull * (nProb + 1));
-    X.extKeys = ctx->extKeys.as<uint32_t>(); X.extVals = ctx->extVals.as<uint32_t>();
-    KL(k_p1_assemble, dim3(gridFor(NC, 256)), dim3(256), 0, ctx->stream, A, X);
     rc = cubScan64(ctx, ctx->rowsBound.as<unsigned long long>(), ctx->stripOff.as<unsigned long long>(), nProb + 1); if (rc) return rc;
     EV1(T_P1);
     TRACE("lanes: p1+scan");
@@ -519,8 +523,9 @@ int stageAlign(ygpu_ctx *ctx)
         // (the cap only ever lowers the count)
         if (useLanes && per * waves > (3ull << 30)) waves = (unsigned)std::min<uint64_t>(waves, std::max<uint64_t>(64, (3ull << 30) / per));
         ENSURE(ctx->scratchAlign, per * waves);
-        ENSURE(ctx->clumpFrags0, 16ull * (ctx->nClumpFrags + 1));
-        HIPCHK(hipMemcpyAsync(ctx->clumpFrags0.p, ctx->clumpFrags.p, 16ull * ctx->nClumpFrags, hipMemcpyDeviceToDevice, ctx->stream));
+        // (k_align extends the fragments in place, a repeated attempt starts from the copy; the lane kernels leave them as they are)
+        if (!useLanes) { ENSURE(ctx->clumpFrags0, 16ull * (ctx->nClumpFrags + 1));
+            HIPCHK(hipMemcpyAsync(ctx->clumpFrags0.p, ctx->clumpFrags.p, 16ull * ctx->nClumpFrags, hipMemcpyDeviceToDevice, ctx->stream)); }
         ENSURE(ctx->rootPush, 4ull * (NC + 1)); ENSURE(ctx->rootBase, 4ull * (NC + 1));
         uint32_t stateOpsCap = (uint32_t)std::min<uint64_t>(0x7FFFFFF0ull, 32ull * NC + 8ull * ctx->nClumpFrags + 65536);
         uint32_t gapOpsPerJoint = 16;
@@ -571,7 +576,7 @@ int stageAlign(ygpu_ctx *ctx)
                 outClumpCap = (uint32_t)std::min<uint64_t>(0x7FFFFFF0ull, 2ull * outClumpCap); outOpsCap = (uint32_t)std::min<uint64_t>(0x7FFFFFF0ull, 2ull * outOpsCap);
                 gapOpsPerJoint = std::min<uint32_t>(gapOpsPerJoint * 2u, 1u << 16); stateOpsCap = (uint32_t)std::min<uint64_t>(0x7FFFFFF0ull, 2ull * stateOpsCap);
             }
-            HIPCHK(hipMemcpyAsync(ctx->clumpFrags.p, ctx->clumpFrags0.p, 16ull * ctx->nClumpFrags, hipMemcpyDeviceToDevice, ctx->stream));
+            if (!useLanes) HIPCHK(hipMemcpyAsync(ctx->clumpFrags.p, ctx->clumpFrags0.p, 16ull * ctx->nClumpFrags, hipMemcpyDeviceToDevice, ctx->stream));
             HIPCHK(hipMemsetAsync(ctx->ctr.as<DevCounters>()->v + C_SCORED, 0, 8 * (16 - C_SCORED), ctx->stream));
         }
         TRACE("align: fetch");
@@ -673,7 +678,7 @@ static int dpBatchLanes(ygpu_ctx *ctx, const ygpu_dp_problem *problems, uint32_t
         const uint32_t gapOpsCap = (uint32_t)std::min<uint64_t>(0x7FFFFFF0ull, gapOpsBound);
         ENSURE(ctx->joints, sizeof(JointRec) * (uint64_t)(nJ + 1)); ENSURE(ctx->sortKeys, 4ull * (nJ + 1)); ENSURE(ctx->sortVals, 4ull * (nJ + 1));
             ENSURE(ctx->sortVals2, 4ull * (nJ + 1));
-        ENSURE(ctx->gapOps, 4ull * gapOpsCap); ENSURE(ctx->slowList, 4ull * (nJ + 1));
+        ENSURE(ctx->gapOps, 4ull * gapOpsCap + 16); ENSURE(ctx->slowList, 4ull * (nJ + 1));
         HIPCHK(hipMemcpyAsync(ctx->joints.p, jp.data(), sizeof(JointRec) * (uint64_t)nJ, hipMemcpyHostToDevice, ctx->stream));
         KL(k_dp_classify, dim3(gridFor(nJ, 256)), dim3(256), 0, ctx->stream, ctx->P, ctx->dBases.as<uint8_t>(), ctx->dFwd.as<uint8_t>(), ctx->dRev.as<uint8_t>(),
             ctx->joints.as<JointRec>(), nJ, ctx->sortKeys.as<uint32_t>(), ctx->sortVals.as<uint32_t>());
