@@ -490,6 +490,37 @@ int  ygpu_bgzf_compress(ygpu_bgzf *h, const void *in, uint64_t n_in, void *out, 
 const char *ygpu_bgzf_last_error(ygpu_bgzf *h);
 int  ygpu_bgzf_close(ygpu_bgzf *h);
 
+/* ---- Coordinate order of a run's BAM records on the device (-obsort; device/bgzf.hip, device/bamsort_stage.h) ------------------------------------------------
+ * A primitive of its own, like ygpu_bgzf: its own stream, device buffers and page-locked staging; it touches no ygpu_ctx.  One handle serves one thread.
+ * open    max_store_bytes caps the device memory of the record store (segments and the per-record arrays); segment_bytes (0: 256 MB) is the size of a
+ *         hipMalloc'd segment of record bytes, window_bytes (0: 1024 payloads of 65 280 bytes) that of a window of the sorted stream, rounded down to a
+ *         multiple of 65 280 and at least 65 280.
+ * append  a batch: n_records whole records in bytes[0 .. n_bytes), record i with keys[i] and lens[i] bytes (their sum is n_bytes).  A record never straddles
+ *         two segments; a batch larger than what is left of the current segment opens a new one, a batch larger than a segment gets one of its own size.
+ *         Passing max_store_bytes (or a refusal of the device) is YGPU_ENOMEM with a message; more than 2^32 - 1 records and an append after sort YGPU_EINVAL.
+ * sort    a stable least-significant-digit radix sort of the keys, 8 bits a pass, the passes whose digit is the same in every key skipped; perm (may be
+ *         null) receives the record number at every sorted place.  Equal keys keep the order they were appended in.
+ * next    window w = bytes [w W, (w + 1) W) of the sorted stream (the records one behind the other in sorted order): gathered on the device, deflated by the
+ *         kernels of ygpu_bgzf_compress, returned as whole BGZF blocks with *n_raw = the window's uncompressed bytes; *n_out == 0: the end.  out_cap must be
+ *         at least ygpu_bgzf_bound(window_bytes).  The blocks of all windows together are the device encoder's blocks of the consecutive payloads of the
+ *         sorted stream, whatever the window size, the segment size and the batches were.  Before sort: YGPU_EINVAL.
+ * info    what = one of YGPU_BAMSORT_*: counters of the handle and the constants a caller needs. */
+typedef struct ygpu_bamsort ygpu_bamsort;
+enum { YGPU_BAMSORT_PASSES = 0,        /* radix passes the last sort ran */
+       YGPU_BAMSORT_SEGMENTS = 1,      /* segments allocated */
+       YGPU_BAMSORT_WINDOWS = 2,       /* windows returned so far */
+       YGPU_BAMSORT_WINDOW_BYTES = 3,  /* W */
+       YGPU_BAMSORT_TILE_KEYS = 4,     /* keys a scatter tile ranks (a workgroup) */
+       YGPU_BAMSORT_STORE_BYTES = 5,   /* device memory of the store now */
+       YGPU_BAMSORT_RECORDS = 6 };
+int  ygpu_bamsort_open(int device, uint64_t max_store_bytes, uint64_t segment_bytes, uint64_t window_bytes, ygpu_bamsort **h);
+int  ygpu_bamsort_append(ygpu_bamsort *h, const void *bytes, uint64_t n_bytes, const uint64_t *keys, const uint32_t *lens, uint32_t n_records);
+int  ygpu_bamsort_sort(ygpu_bamsort *h, uint32_t *perm /* n entries, may be null */);
+int  ygpu_bamsort_next(ygpu_bamsort *h, void *out, uint64_t out_cap, uint64_t *n_out, uint64_t *n_raw);
+uint64_t ygpu_bamsort_info(ygpu_bamsort *h, int what);
+const char *ygpu_bamsort_last_error(ygpu_bamsort *h);
+int  ygpu_bamsort_close(ygpu_bamsort *h);
+
 /* `yaha -g genome.fa [-L k] [-S s] [-H h]`: writes genome.nib2 and genome.X<LL>_<SS>_<HHHHH>S (Main.c:554-628). */
 int  yaha_build_index(int argc, const char *const *argv);
 /* The complete command-line program (index creation or query alignment on the GPU). */

@@ -52,6 +52,13 @@ uint64_t ygpu_bgzf_bound(uint64_t n) { return (n + 65279) / 65280 * 65536; }
 int  ygpu_bgzf_compress(ygpu_bgzf *, const void *, uint64_t, void *, uint64_t, uint64_t *) { return YGPU_ENODEV; }
 const char *ygpu_bgzf_last_error(ygpu_bgzf *) { return "sanitizer build: no device code"; }
 int  ygpu_bgzf_close(ygpu_bgzf *) { return 0; }
+int  ygpu_bamsort_open(int, uint64_t, uint64_t, uint64_t, ygpu_bamsort **h) { if (h) *h = nullptr; return YGPU_ENODEV; }      // (host/bam.cpp then keeps and orders the records on the host)
+int  ygpu_bamsort_append(ygpu_bamsort *, const void *, uint64_t, const uint64_t *, const uint32_t *, uint32_t) { return YGPU_ENODEV; }
+int  ygpu_bamsort_sort(ygpu_bamsort *, uint32_t *) { return YGPU_ENODEV; }
+int  ygpu_bamsort_next(ygpu_bamsort *, void *, uint64_t, uint64_t *, uint64_t *) { return YGPU_ENODEV; }
+uint64_t ygpu_bamsort_info(ygpu_bamsort *, int) { return 0; }
+const char *ygpu_bamsort_last_error(ygpu_bamsort *) { return "sanitizer build: no device code"; }
+int  ygpu_bamsort_close(ygpu_bamsort *) { return 0; }
 void *ygpu_host_alloc(size_t) { return nullptr; }
 void ygpu_host_free(void *) {}
 int  ygpu_submit(ygpu_ctx *, const ygpu_read_batch *, ygpu_ticket *) { return YGPU_ENODEV; }

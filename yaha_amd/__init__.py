@@ -167,6 +167,7 @@ EXPORTS = (
     "ygpu_indels_enable", "ygpu_indels_size", "ygpu_indels_collect", "yaha_session_indel_params",
     "ygpu_junctions_enable", "ygpu_junctions_size", "ygpu_junctions_collect", "yaha_session_junction_params",
     "ygpu_bgzf_open", "ygpu_bgzf_bound", "ygpu_bgzf_compress", "ygpu_bgzf_last_error", "ygpu_bgzf_close",
+    "ygpu_bamsort_open", "ygpu_bamsort_append", "ygpu_bamsort_sort", "ygpu_bamsort_next", "ygpu_bamsort_info", "ygpu_bamsort_last_error", "ygpu_bamsort_close",
     "ygpu_submit", "ygpu_poll", "ygpu_wait", "ygpu_seed_join", "ygpu_chain", "ygpu_dp_batch", "ygpu_dp_batch_ex",
     "yaha_session_open", "yaha_session_close", "yaha_session_error", "yaha_session_params",
     "yaha_session_index_view", "yaha_session_header", "yaha_session_next_batch", "yaha_session_emit", "yaha_session_postfilter_params", "yaha_session_emit_filtered",
@@ -189,6 +190,10 @@ def lib():
         L.ygpu_bgzf_last_error.argtypes = [C.c_void_p]
         L.ygpu_bgzf_bound.restype = C.c_uint64
         L.ygpu_bgzf_bound.argtypes = [C.c_uint64]
+        L.ygpu_bamsort_last_error.restype = C.c_char_p
+        L.ygpu_bamsort_last_error.argtypes = [C.c_void_p]
+        L.ygpu_bamsort_info.restype = C.c_uint64
+        L.ygpu_bamsort_info.argtypes = [C.c_void_p, C.c_int]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -552,6 +557,87 @@ class Bgzf:
     def close(self):
         if self._h:
             lib().ygpu_bgzf_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class BamSortError(RuntimeError):
+    """A ygpu_bamsort_* call that failed: .code is the YGPU_E* value, the text carries the handle's message."""
+
+    def __init__(self, what, code, msg):
+        RuntimeError.__init__(self, "%s failed: %d %s" % (what, code, msg))
+        self.code = code
+
+
+class BamSort:
+    """The coordinate order of BAM records on the device (ygpu_bamsort_*): a handle of its own that touches no Context.  append(bytes, keys, lens) adds a batch
+    of whole records (keys: uint64, lens: the records' byte counts, which add up to len(bytes)); sort() orders them -- stable: equal keys keep append order --
+    and returns the permutation (numpy uint32: the record number at every sorted place); windows() yields (blocks, n_raw) for every window of window_bytes of
+    the sorted stream: whole BGZF blocks without the end-of-file block, and the uncompressed bytes they hold.  segment_bytes / window_bytes 0: the defaults
+    (256 MB; 1024 payloads of 65 280 bytes)."""
+
+    PASSES, SEGMENTS, WINDOWS, WINDOW_BYTES, TILE_KEYS, STORE_BYTES, RECORDS = range(7)
+
+    def __init__(self, max_store_bytes, segment_bytes=0, window_bytes=0, device=0):
+        self._h = C.c_void_p()
+        rc = lib().ygpu_bamsort_open(device, C.c_uint64(max_store_bytes), C.c_uint64(segment_bytes), C.c_uint64(window_bytes), C.byref(self._h))
+        if rc != 0:
+            msg = lib().ygpu_bamsort_last_error(self._h).decode() if self._h else ""
+            self.close()
+            raise BamSortError("ygpu_bamsort_open", rc, msg)
+
+    def _check(self, what, rc):
+        if rc != 0:
+            raise BamSortError(what, rc, lib().ygpu_bamsort_last_error(self._h).decode())
+
+    def info(self, what):
+        return int(lib().ygpu_bamsort_info(self._h, what))
+
+    @staticmethod
+    def tile_keys():
+        """Keys a scatter tile of the radix sort ranks (a workgroup)."""
+        return int(lib().ygpu_bamsort_info(None, BamSort.TILE_KEYS))
+
+    @property
+    def passes(self):
+        return self.info(self.PASSES)
+
+    def append(self, data, keys, lens):
+        import numpy as np
+        data = bytes(data)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64); lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        assert len(keys) == len(lens)
+        self._check("ygpu_bamsort_append", lib().ygpu_bamsort_append(self._h, data, C.c_uint64(len(data)), keys.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
+                                                                     C.c_uint32(len(keys))))
+
+    def sort(self):
+        import numpy as np
+        perm = np.zeros(self.info(self.RECORDS), dtype=np.uint32)
+        self._check("ygpu_bamsort_sort", lib().ygpu_bamsort_sort(self._h, perm.ctypes.data_as(C.c_void_p)))
+        return perm
+
+    def next(self):
+        """(blocks, n_raw) of the next window; (b"", 0) at the end."""
+        cap = int(lib().ygpu_bgzf_bound(self.info(self.WINDOW_BYTES)))
+        out = C.create_string_buffer(cap); n = C.c_uint64(); raw = C.c_uint64()
+        self._check("ygpu_bamsort_next", lib().ygpu_bamsort_next(self._h, out, C.c_uint64(cap), C.byref(n), C.byref(raw)))
+        return out.raw[:n.value], int(raw.value)
+
+    def windows(self):
+        while True:
+            blocks, n_raw = self.next()
+            if not blocks:
+                return
+            yield blocks, n_raw
+
+    def close(self):
+        if self._h:
+            lib().ygpu_bamsort_close(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):

@@ -21,7 +21,7 @@ static void usage(FILE *o)
           "  yaha -g genome.{fa|fna|fasta} -c   (compress to genome.nib2 only)      yaha -g genome.nib2 -u   (back to genome.fasta)\n"
           "       (built on the GPU when one is visible and -S is 1; -cpuindex forces the host builder; the files are identical)\n\n"
           "Query alignment (hot path on MI355X):\n"
-          "  yaha -x indexFile [-q queryFile|(stdin)] [-o8|(-osh)|-oss|-obh|-obs outFile|(stdout)] [-t hostThreads (1)]\n"
+          "  yaha -x indexFile [-q queryFile|(stdin)] [-o8|(-osh)|-oss|-obh|-obs outFile|(stdout)] [-obsort [-sortmem GB (32)]] [-t hostThreads (1)]\n"
           "       [-gpus N (1)] [-ctx contextsPerGpu (3)] [-device D (0)] [-batch readsPerBatch (about 16 M bases)] [-dpf Y|N (Y: post-filter on the device)]\n"
           "  general : [-BW 5] [-G 50] [-H 650] [-M 25] [-MD 50] [-P 0.9] [-X 25]\n"
           "  scoring : [-AGS Y|N] [-GEC 2] [-GOC 5] [-MS 1] [-RC 3]\n"
@@ -29,6 +29,13 @@ static void usage(FILE *o)
           "  -o8 modified Blast8, -osh SAM hard clipping, -oss SAM soft clipping.\n"
           "  -obh BAM hard clipping, -obs BAM soft clipping: the records of -osh / -oss in BAM's layout, unsorted, in BGZF blocks deflated on the device\n"
           "       (fixed Huffman codes; YAHA_HOST_BGZF=1: on the host).  The blocks' boundaries follow -batch and -ctx, the decompressed stream does not.\n"
+          "  -obsort (with -obh / -obs FILE) [-sortmem GB (32)]: the BAM in coordinate order -- sequence, position, equal keys in print order -- and its index\n"
+          "       FILE.bai, both written after the last alignment; the decompressed stream does not depend on -batch, -ctx, -gpus or -t.  The whole run's records\n"
+          "       stay in the memory of device -device until then (about 1.7 KB per 1 kbp read with qualities; -sortmem caps it), are ordered there by a radix\n"
+          "       sort and go from there into the deflate kernels.  There is NO spill: sorted runs are not written to disk and merged -- when the store would pass\n"
+          "       -sortmem the run stops, says so and leaves no file behind.  A sequence over 2^29 bases cannot be indexed by BAI: the run stops before the\n"
+          "       first batch.  YAHA_HOST_BAMSORT=1: store and order on the host; YAHA_SORTMEM_BYTES=N: the cap in bytes (for tests).  Errors in these two\n"
+          "       options leave with exit code 2.\n"
           "  depth   : [-ocov depthFile|stdout] [-covbin basesPerBin (100)] [-covq minMapQ (0)]\n"
           "       read depth of the printed records along the reference (bases under M of the CIGAR) as bedGraph, written after the last alignment;\n"
           "       accumulated on the device behind its post-filter: 4 bytes a bin of device memory per GPU -- -covbin 1 on a 3.1 Gbp genome is 12.4 GB beside the\n"
@@ -103,6 +110,10 @@ int parseArgs(int argc, char **argv, Args &a)
         // BAM: the SAM writer's records in binary, hard (-obh) or soft (-obs) clipped; an output selector like the three above -- the last one given wins
         else if (is("-obh") || is("-obs")) { a.outputBlast8 = false; a.outputSAM = true; a.outputBAM = true; a.hardClip = is("-obh"); const char *v = val();
             a.ofileName = (!strcmp(v, "-stdout")) ? "stdout" : v; a.haveO = true; }
+        // -obsort: the BAM of -obh / -obs in coordinate order with its index; -sortmem: the cap of the record store in GB
+        else if (is("-obsort")) a.bamSort = true;
+        else if (is("-sortmem")) { if (!parseInt(val(), "-sortmem", a.sortMemGB)) return 3; a.haveSortMem = true;
+            if (a.sortMemGB < 1) { fprintf(stderr, "-sortmem must be at least 1 (GB).\n\n"); usage(stderr); return 3; } }
         else if (is("-t")) { if (!parseInt(val(), "-t", a.numThreads)) return 2; }
         else if (is("-v")) a.verbose = true;
         else if (is("-x")) { a.xfileName = val(); a.haveX = true; query = true; index = false; }
@@ -208,6 +219,11 @@ int parseArgs(int argc, char **argv, Args &a)
     if (a.haveId && a.idFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout") || (a.haveBp && a.bpFileName == "stdout")
         || (a.havePu && a.puFileName == "stdout"))) {
         fprintf(stderr, "-oid stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
+    // the sorted BAM: an option of -obh / -obs with a file of its own beside theirs
+    if (a.haveSortMem && !a.bamSort) { fprintf(stderr, "-sortmem needs -obsort.\n\n"); usage(stderr); return 3; }
+    if (a.bamSort && !query) { fprintf(stderr, "-obsort is an option of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return 3; }
+    if (a.bamSort && !a.outputBAM) { fprintf(stderr, "-obsort needs -obh or -obs as the output selector (the last one given wins).\n\n"); usage(stderr); return 3; }
+    if (a.bamSort && a.ofileName == "stdout") { fprintf(stderr, "-obsort writes FILE and FILE.bai: the BAM cannot go to standard output.\n\n"); usage(stderr); return 3; }
     if ((a.compress || a.uncompress) && !query) {                                                  // Main.c:472-533: -c wants a FASTA genome, -u a .nib2
         if (!a.haveG) { fprintf(stderr, "Genome file specification (-g) is required for index creation.\n\n"); usage(stderr); return 2; }
         size_t dot = a.gfileName.rfind('.'); const std::string ext = dot == std::string::npos ? "" : a.gfileName.substr(dot);
@@ -262,10 +278,11 @@ void paramsFromArgs(const Args &a, ygpu_params &p)
 std::string samHeader(const Args &a, const Genome &g)                   // outputFileHeader, AlignOutput.c:30-111
 {
     if (!a.outputSAM) return "";
-    std::string h = "@HD\tVN:1.0\n"; char buf[512];
+    std::string h = a.bamSort ? "@HD\tVN:1.0\tSO:coordinate\n" : "@HD\tVN:1.0\n"; char buf[512];
     for (auto &s : g.seqs) { h += "@SQ\tSN:" + s.name; snprintf(buf, sizeof buf, "\tLN:%u\n", s.length); h += buf; }
     h += "@PG\tID:YAHA\tVN:0.1.83\tCL:yaha";
     h += " -q " + a.qfileName + " -x " + a.xfileName; h += a.outputBAM ? (a.hardClip ? " -obh " : " -obs ") : a.hardClip ? " -osh " : " -oss "; h += a.ofileName;
+    if (a.bamSort) h += " -obsort";
     snprintf(buf, sizeof buf, " -t %d -BW %d -G %d -H %d -M %d -MD %d -P %4.2f -X %d", a.numThreads, a.bandWidth, a.maxGap, a.maxHits, a.minMatch, a.maxDesert, a.minIdentity,
         a.XCutoff); h += buf;
     if (a.affineGapScoring) { snprintf(buf, sizeof buf, " -AGS Y -GEC %d -GOC %d -MS %d -RC %d", a.GECost, a.GOCost, a.MScore, a.RCost); h += buf; } else h += " -AGS N";

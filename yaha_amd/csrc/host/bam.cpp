@@ -11,6 +11,8 @@
 // compiles as well) does the work.  A compression that FAILS on the device is an error of the run, not a reason to fall back.
 #include "yaha_host.h"
 #include "../bgzf_core.h"
+#include "../bai_core.h"
+#include <chrono>
 
 extern "C" {
 __attribute__((weak)) int ygpu_bgzf_open(int device, uint64_t max_in_bytes, ygpu_bgzf **h);
@@ -18,6 +20,13 @@ __attribute__((weak)) uint64_t ygpu_bgzf_bound(uint64_t n_in);
 __attribute__((weak)) int ygpu_bgzf_compress(ygpu_bgzf *h, const void *in, uint64_t n_in, void *out, uint64_t out_cap, uint64_t *n_out);
 __attribute__((weak)) const char *ygpu_bgzf_last_error(ygpu_bgzf *h);
 __attribute__((weak)) int ygpu_bgzf_close(ygpu_bgzf *h);
+__attribute__((weak)) int ygpu_bamsort_open(int device, uint64_t max_store_bytes, uint64_t segment_bytes, uint64_t window_bytes, ygpu_bamsort **h);
+__attribute__((weak)) int ygpu_bamsort_append(ygpu_bamsort *h, const void *bytes, uint64_t n_bytes, const uint64_t *keys, const uint32_t *lens, uint32_t n_records);
+__attribute__((weak)) int ygpu_bamsort_sort(ygpu_bamsort *h, uint32_t *perm);
+__attribute__((weak)) int ygpu_bamsort_next(ygpu_bamsort *h, void *out, uint64_t out_cap, uint64_t *n_out, uint64_t *n_raw);
+__attribute__((weak)) uint64_t ygpu_bamsort_info(ygpu_bamsort *h, int what);
+__attribute__((weak)) const char *ygpu_bamsort_last_error(ygpu_bamsort *h);
+__attribute__((weak)) int ygpu_bamsort_close(ygpu_bamsort *h);
 }
 
 namespace yaha {
@@ -73,7 +82,7 @@ std::string bamHeader(const Args &a, const Genome &g)
     return h;
 }
 
-bool bamRecord(const Args &a, const Genome &g, const Read &r, const OutClump &oc, int primaryCount, Text &out)
+bool bamRecord(const Args &a, const Genome &g, const Read &r, const OutClump &oc, int primaryCount, Text &out, BamEntry *entry)
 {
     const ygpu_clump &c = oc.c;
     uint32_t seqStart = c.sro, seqEnd = c.sro + c.refLen - 1;
@@ -94,7 +103,8 @@ bool bamRecord(const Args &a, const Genome &g, const Read &r, const OutClump &oc
     if (a.hardClip) { qstart = c.sqo; qend = c.eqo; }
     const uint32_t lseq = qend >= qstart ? (uint32_t)(qend - qstart + 1) : 0u;
     w = put32(w, (uint32_t)si); w = put32(w, seqStart); w = put8(w, (uint32_t)idLen + 1u); w = put8(w, oc.mapQuality);
-    w = put16(w, reg2bin(seqStart, std::max(seqStart, seqEnd) + 1u));
+    const uint32_t endExcl = std::max(seqStart, seqEnd) + 1u, bin = reg2bin(seqStart, endExcl);
+    w = put16(w, bin);
     uint8_t *const nCigarAt = w; w += 2;
     w = put16(w, reversed ? 0x10 : 0); w = put32(w, lseq); w = put32(w, 0xFFFFFFFFu); w = put32(w, 0xFFFFFFFFu); w = put32(w, 0);
     memcpy(w, r.id.data(), idLen); w += idLen; *w++ = 0;
@@ -150,6 +160,7 @@ bool bamRecord(const Args &a, const Genome &g, const Read &r, const OutClump &oc
     }
     ybgzf::put32(w0, (uint32_t)(w - w0) - 4u);
     out.len += (size_t)(w - w0);
+    if (entry) *entry = BamEntry{(uint32_t)si, seqStart, (uint32_t)(w - w0), endExcl, bin};
     return true;
 }
 
@@ -198,6 +209,136 @@ int BgzfPacker::pack(int device, const char *in, size_t n, Text &out, BamStats &
         at += (size_t)(b[16] | b[17] << 8) + 1u;
     }
     st.blocks += blocks; st.blocksStored += stored; st.bytesRaw += n; st.bytesWritten += out.len; st.deviceBatches++;
+    return 0;
+}
+
+// ---- -obsort ------------------------------------------------------------------------------------------------------------------------------------------------------
+struct BamSorter::Impl {
+    int device = 0; uint64_t cap = 0; ygpu_bamsort *h = nullptr; bool host = false;
+    std::vector<BamEntry> entries;                                                    // every record of the run, in append (= print) order: 20 bytes a record
+    Text store; std::vector<uint64_t> at;                                             // host store: the records' bytes and where each starts
+    std::vector<uint64_t> keys; std::vector<uint32_t> lens;                           // (a batch's, reused)
+};
+
+static double msNow() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+BamSorter::BamSorter(int device, uint64_t capBytes) : impl(new Impl)
+{
+    Impl &I = *impl; I.device = device; I.cap = capBytes;
+    const bool have = ygpu_bamsort_open != nullptr && ygpu_bamsort_append != nullptr && ygpu_bamsort_sort != nullptr && ygpu_bamsort_next != nullptr &&
+        ygpu_bamsort_info != nullptr && ygpu_bamsort_last_error != nullptr && ygpu_bamsort_close != nullptr && ygpu_bgzf_bound != nullptr;
+    I.host = !have || getenv("YAHA_HOST_BAMSORT") != nullptr;
+    if (!I.host && ygpu_bamsort_open(device, capBytes, 0, 0, &I.h) != 0) {
+        fprintf(stderr, "-obsort: no record store on device %d (%s): the records are kept and ordered on the host.\n", device, I.h ? ygpu_bamsort_last_error(I.h)
+            : "no handle was made");
+        if (I.h) { ygpu_bamsort_close(I.h); I.h = nullptr; }
+        I.host = true;
+    }
+    stats.device = !I.host;
+}
+BamSorter::~BamSorter() { if (impl->h && getenv("YAHA_FAST_EXIT") == nullptr) ygpu_bamsort_close(impl->h); delete impl; }
+
+int BamSorter::append(const char *bytes, size_t n, const BamEntry *e, size_t nEntries, std::string &err)
+{
+    Impl &I = *impl; const double t0 = msNow();
+    if (nEntries == 0) return 0;
+    if (I.entries.size() + nEntries > 0xFFFFFFFFull) { err = "-obsort: more than 2^32 - 1 records"; return YGPU_EINVAL; }
+    if (I.host) {
+        if ((uint64_t)I.store.len + n + 20ull * (I.entries.size() + nEntries) > I.cap) {
+            err = "-obsort: the record store would pass -sortmem (" + std::to_string(I.cap) + " bytes) -- there is no spill: give a larger -sortmem or sort the unsorted output";
+            return YGPU_ENOMEM; }
+        uint64_t p = I.store.len;
+        try { I.store.append(bytes, n); for (size_t i = 0; i < nEntries; i++) { I.at.push_back(p); p += e[i].len; } }
+        catch (const std::bad_alloc &) { err = "-obsort: the host cannot give the memory for the record store (-sortmem " + std::to_string(I.cap) + " bytes)"; return YGPU_ENOMEM; }
+    } else {
+        I.keys.resize(nEntries); I.lens.resize(nEntries);
+        for (size_t i = 0; i < nEntries; i++) { I.keys[i] = ybai::sortKey(e[i].ref, e[i].pos); I.lens[i] = e[i].len; }
+        const int rc = ygpu_bamsort_append(I.h, bytes, n, I.keys.data(), I.lens.data(), (uint32_t)nEntries);
+        if (rc != 0) { err = std::string("-obsort: the record store on device ") + std::to_string(I.device) + " (-sortmem " + std::to_string(I.cap) + " bytes): " +
+            ygpu_bamsort_last_error(I.h); return rc; }
+    }
+    I.entries.insert(I.entries.end(), e, e + nEntries);
+    stats.records = I.entries.size(); msAppend += msNow() - t0;
+    return 0;
+}
+
+int BamSorter::finish(FILE *out, const std::string &baiPath, const std::string &rawHeader, size_t nRefs, BamStats &st, std::string &err)
+{
+    Impl &I = *impl; const bool timing = getenv("YAHA_TIMING") != nullptr; const double t0 = msNow();
+    const size_t n = I.entries.size();
+    // the order: perm[j] = the record at sorted place j
+    std::vector<uint32_t> perm(n);
+    if (I.host) {
+        bamSortOrder(I.entries.data(), n, perm.data());
+    } else {
+        const int rc = ygpu_bamsort_sort(I.h, perm.data());
+        if (rc != 0) { err = std::string("-obsort: the sort on device ") + std::to_string(I.device) + " failed: " + ygpu_bamsort_last_error(I.h); return rc; }
+        stats.passes = ygpu_bamsort_info(I.h, YGPU_BAMSORT_PASSES); stats.segments = ygpu_bamsort_info(I.h, YGPU_BAMSORT_SEGMENTS);
+    }
+    std::vector<BamEntry> sorted(n);
+    for (size_t j = 0; j < n; j++) { if (perm[j] >= n) { err = "-obsort: the permutation is out of range"; return YGPU_EINTERNAL; } sorted[j] = I.entries[perm[j]]; }
+    for (size_t j = 1; j < n; j++) if (ybai::sortKey(sorted[j - 1].ref, sorted[j - 1].pos) > ybai::sortKey(sorted[j].ref, sorted[j].pos) ||
+        (ybai::sortKey(sorted[j - 1].ref, sorted[j - 1].pos) == ybai::sortKey(sorted[j].ref, sorted[j].pos) && perm[j - 1] > perm[j])) {
+        err = "-obsort: the records are not in stable coordinate order at place " + std::to_string(j); return YGPU_EINTERNAL; }
+    const double t1 = msNow();
+    if (timing) fprintf(stderr, "[yaha] -obsort: %zu records appended in %.1f ms (all batches), ordered %s in %.1f ms\n", n, msAppend, I.host ? "on the host" : "on the device",
+        t1 - t0);
+    // the header's blocks, from the host's encoder
+    auto put = [&](const char *p, size_t len) { if (len && fwrite(p, 1, len, out) != len) { err = "Failure writing the output file."; return false; } return true; };
+    Text packed; uint64_t fileAt = 0;
+    { BgzfPacker hostPacker; hostPacker.packHost(rawHeader.data(), rawHeader.size(), packed, st); if (!put(packed.p, packed.len)) return YGPU_EINTERNAL; fileAt = packed.len; }
+    // the sorted stream's blocks, window by window; the file offset of every block
+    uint64_t total = 0; for (size_t j = 0; j < n; j++) total += sorted[j].len;
+    std::vector<uint64_t> coffs((size_t)ybgzf::blocksOf(total) + 1); size_t nBlocks = 0;
+    auto account = [&](const Text &blk) {
+        const uint64_t end = ybai::blockOffsets((const uint8_t *)blk.p, blk.len, fileAt, coffs.data(), &nBlocks, coffs.size() - 1);
+        if (end == 0) { err = "-obsort: a window's blocks do not add up"; return false; }
+        fileAt = end; stats.windows++; return true; };
+    if (I.host) {
+        const uint64_t W = 1024ull * ybgzf::PAYLOAD_MAX; BgzfPacker packer; Text win; size_t j = 0; uint64_t inRec = 0;
+        for (uint64_t w0 = 0; w0 < total; w0 += W) {
+            const double tw = msNow(); const uint64_t wn = std::min<uint64_t>(W, total - w0); win.clear(); win.room((size_t)wn);
+            while (win.len < wn) {                                                    // the records of the window, the first and the last possibly in part
+                const BamEntry &e = sorted[j]; const uint64_t take = std::min<uint64_t>(e.len - inRec, wn - win.len);
+                win.append(I.store.p + I.at[perm[j]] + inRec, (size_t)take); inRec += take;
+                if (inRec == e.len) { j++; inRec = 0; }
+            }
+            std::string perr; const int rc = packer.pack(I.device, win.p, win.len, packed, st, perr);
+            if (rc != 0) { err = "BGZF compression on device " + std::to_string(I.device) + " failed: " + perr; return rc; }
+            if (!account(packed) || !put(packed.p, packed.len)) return YGPU_EINTERNAL;
+            if (timing) fprintf(stderr, "[yaha] -obsort: window %llu: %llu bytes to %zu in %.1f ms (host store)\n", (unsigned long long)(w0 / W), (unsigned long long)wn,
+                packed.len,
+                msNow() - tw);
+        }
+    } else {
+        const uint64_t room = ygpu_bgzf_bound(ygpu_bamsort_info(I.h, YGPU_BAMSORT_WINDOW_BYTES));
+        for (uint64_t w = 0;; w++) {
+            const double tw = msNow(); uint64_t got = 0, nRaw = 0; packed.clear();
+            const int rc = ygpu_bamsort_next(I.h, packed.room((size_t)room), room, &got, &nRaw);
+            if (rc != 0) { err = std::string("-obsort: window ") + std::to_string(w) + " on device " + std::to_string(I.device) + " failed: " + ygpu_bamsort_last_error(I.h);
+                return rc; }
+            if (got == 0) break;
+            packed.len = (size_t)got;
+            const size_t before = nBlocks;
+            if (!account(packed) || !put(packed.p, packed.len)) return YGPU_EINTERNAL;
+            uint64_t stored = 0;
+            for (size_t b = before; b < nBlocks; b++) if ((((const uint8_t *)packed.p)[coffs[b] - coffs[before] + ybgzf::HEADER] & 6u) == 0) stored++;
+            st.blocks += nBlocks - before; st.blocksStored += stored; st.bytesRaw += nRaw; st.bytesWritten += got; st.deviceBatches++;
+            if (timing) fprintf(stderr, "[yaha] -obsort: window %llu: %llu bytes to %llu in %.1f ms (gather, deflate, download)\n", (unsigned long long)w, (unsigned long long)nRaw,
+                (unsigned long long)got, msNow() - tw);
+        }
+    }
+    if (nBlocks != ybgzf::blocksOf(total)) { err = "-obsort: " + std::to_string(nBlocks) + " blocks were written, the stream has " + std::to_string(ybgzf::blocksOf(total));
+        return YGPU_EINTERNAL; }
+    coffs[nBlocks] = fileAt;
+    Text eof; bgzfEof(eof); st.bytesWritten += eof.len; if (!put(eof.p, eof.len)) return YGPU_EINTERNAL;
+    if (fflush(out) != 0) { err = "Failure writing the output file."; return YGPU_EINTERNAL; }
+    const double t2 = msNow();
+    const std::string bai = baiBuild(sorted.data(), n, nRefs, coffs.data(), nBlocks);
+    std::string werr; if (!writeFile(baiPath.c_str(), bai.data(), bai.size(), werr)) { err = werr; return YGPU_EINTERNAL; }
+    stats.baiBytes = bai.size();
+    if (timing) fprintf(stderr, "[yaha] -obsort: %llu windows written in %.1f ms, the index (%zu bytes) in %.1f ms\n", (unsigned long long)stats.windows, t2 - t1, bai.size(),
+        msNow() - t2);
     return 0;
 }
 

@@ -33,6 +33,7 @@ struct yaha_session {
     // -oid: the formatters walk the records the device did not count (indels.cpp) into a list of their own, merged into the run's alleles once per batch
     const IndelTrack *indels = nullptr; IndelTrack::Local idLocal;
     uint64_t bamRecords = 0;                                         // -obh / -obs: records written into the text (the formatters: per batch)
+    std::vector<BamEntry> *bamEntries = nullptr;                     // -obsort: one entry per record written, in the order of the text (the batch's list)
 };
 
 namespace yaha {
@@ -143,7 +144,8 @@ enum : unsigned { kJunctionsOnDevice = 1u << 31, kIndelsOnDevice = 1u << 30 };
 // one record of read i: its text, and its share of every binned track the device did not count it for
 static inline void emitRecord(yaha_session *s, uint32_t i, const OutClump &o, int primaryCount, Text &text, unsigned onDevice = 0)
 {
-    if (s->args.outputBAM) { if (bamRecord(s->args, s->genome, s->reads[i], o, primaryCount, text)) s->bamRecords++; }
+    if (s->args.outputBAM) { BamEntry e; if (bamRecord(s->args, s->genome, s->reads[i], o, primaryCount, text, s->bamEntries ? &e : nullptr)) { s->bamRecords++;
+        if (s->bamEntries) s->bamEntries->push_back(e); } }
     else printClump(s->args, s->genome, s->reads[i], o, primaryCount, text);
     for (size_t t = 0; t < s->tracks.size(); t++) if (!(onDevice >> t & 1u)) s->tracks[t]->add(o, s->reads[i]);
     if (s->indels && !(onDevice & kIndelsOnDevice)) s->indels->add(o, s->reads[i], s->idLocal);
@@ -280,7 +282,17 @@ int runQueries(Args &a, FILE *log)
     setvbuf(out, nullptr, _IONBF, 0);                                       // whole batches are written with one call each
     // -obh / -obs: the header is BGZF blocks of its own from the host's encoder; every batch's records are compressed by the thread that formats them (bam.cpp) and
     // the end-of-file block follows the last batch
-    BamStats bam;
+    // -obsort: nothing is written before the last alignment -- the records go into the sorter (bam.cpp: a store on device -device, or the host's), which writes the
+    // header's blocks, the sorted stream's and FILE.bai at the end; a failed run leaves neither file behind
+    BamStats bam; std::unique_ptr<BamSorter> sorter; const std::string baiName = A.ofileName + ".bai";
+    auto dropSorted = [&]() { if (out != stdout) { fclose(out); out = nullptr; } remove(A.ofileName.c_str()); remove(baiName.c_str()); };
+    if (A.bamSort) {
+        for (auto &sq : S->genome.seqs) if (sq.length > (1u << 29)) {
+            fprintf(log, "-obsort: sequence %s has %u bases; BAI indexes sequences of up to 2^29 = 536870912 bases.\n", sq.name.c_str(), sq.length); dropSorted(); return 1; }
+        uint64_t capBytes = (uint64_t)A.sortMemGB << 30;
+        if (const char *e = getenv("YAHA_SORTMEM_BYTES")) { const long long v = atoll(e); if (v > 0) capBytes = (uint64_t)v; }      // (byte-granular, for tests)
+        sorter.reset(new BamSorter(A.device, capBytes));
+    } else
     if (A.outputBAM) {
         const std::string raw = bamHeader(A, S->genome); Text packed; BgzfPacker hostPacker; hostPacker.packHost(raw.data(), raw.size(), packed, bam);
         if (fwrite(packed.p, 1, packed.len, out) != packed.len) { fprintf(log, "Failure writing the output file.\n"); return 1; }
@@ -319,7 +331,7 @@ int runQueries(Args &a, FILE *log)
                    // -obp: the junctions the device made of the batch and its statistics; the ones the formatter made, and its counts
                    std::vector<ygpu_junction> jnDev, jnHost; uint64_t jnDevStats[4] = {0, 0, 0, 0}, jnHostReads = 0, jnHostSkipped = 0;
                    // -obh / -obs: the device the batch ran on, its records as BGZF blocks, the time their compression took
-                   int dev = 0; Text packed; double tPack = 0;
+                   int dev = 0; Text packed; double tPack = 0; std::vector<BamEntry> entries;
                    double tRead = 0, tDev = 0, tFmt = 0; };
     typedef std::unique_ptr<Batch> BatchP;
     struct Pool { std::mutex mu; std::vector<BatchP> free; BatchP get() { { std::lock_guard<std::mutex> lk(mu); if (!free.empty()) { BatchP b = std::move(free.back());
@@ -596,7 +608,7 @@ int runQueries(Args &a, FILE *log)
         std::unique_ptr<BgzfPacker> packer; if (A.outputBAM) packer.reset(new BgzfPacker);
         BatchP b;
         while (fmtQ.pop(b)) {
-            const double t0 = now(); b->text.clear();
+            const double t0 = now(); b->text.clear(); b->entries.clear(); local.bamEntries = sorter ? &b->entries : nullptr;
             b->jnHost.clear(); local.jnOut = &b->jnHost; local.jnReads = local.jnSkipped = 0;
             if (!(b->nReads && b->filtered && (b->onDevice & kJunctionsOnDevice))) { b->jnDev.clear(); b->onDevice &= ~kJunctionsOnDevice;
                 memset(b->jnDevStats, 0, sizeof b->jnDevStats); }
@@ -614,7 +626,8 @@ int runQueries(Args &a, FILE *log)
             b->jnHostReads = local.jnReads; b->jnHostSkipped = local.jnSkipped;
             if (indels) indels->merge(local.idLocal);
             b->tFmt = now() - t0;
-            if (packer) {                                                      // (a batch without records is no block: an empty one would read as the end of the file)
+            if (sorter) { bam.records += local.bamRecords; local.bamRecords = 0; }      // (-obsort: the raw records travel to the writer, nothing is compressed here)
+            else if (packer) {                                                 // (a batch without records is no block: an empty one would read as the end of the file)
                 std::string perr; b->packed.clear();
                 const int prc = stop ? 0 : packer->pack(b->dev, b->text.p, b->text.len, b->packed, bam, perr);
                 if (prc != 0) { char m[640]; snprintf(m, sizeof m, "BGZF compression on device %d failed (%d): %s", b->dev, prc, perr.c_str()); fail(m); }
@@ -633,12 +646,19 @@ int runQueries(Args &a, FILE *log)
             while (!done.empty() && done.begin()->first == nextOut) {
                 BatchP w = std::move(done.begin()->second); done.erase(done.begin()); nextOut++; ticketsWritten = nextOut;
                 if (!stop) {
-                    const Text &bytes = A.outputBAM ? w->packed : w->text;
+                    const Text &bytes = A.outputBAM ? w->packed : w->text; std::string serr;
+                    // -obsort: appended in ticket order -- what makes equal keys keep print order
+                    if (sorter) { if (sorter->append(w->text.p, w->text.len, w->entries.data(), w->entries.size(), serr) != 0) fail(serr.c_str());
+                        else { const double t = now(); if (nWritten == 0) { tFirstOut = t; nFirst = w->nReads; } tLastOut = t; nWritten += w->nReads; } }
+                    else
                     if (bytes.len && fwrite(bytes.p, 1, bytes.len, out) != bytes.len) fail("Failure writing the output file");
                     else { const double t = now(); if (nWritten == 0) { tFirstOut = t; nFirst = w->nReads; } tLastOut = t; nWritten += w->nReads; }
                     if (junctions && w->nReads) junctions->addBatch(w->jnDev.data(), w->jnDev.size(), w->jnDevStats, w->jnHost, w->jnHostReads, w->jnHostSkipped);
                     if (timing) fprintf(stderr, "[yaha] ticket %llu: %zu reads  parse %.1f  device (upload, run, collect) %.1f  format %.1f ms  written at %.1f\n",
                         (unsigned long long)w->ticket, w->nReads, w->tRead, w->tDev, w->tFmt, now() - tEnter);
+                    if (timing && sorter) fprintf(stderr, "[yaha] ticket %llu: %zu records (%zu bytes) appended to the sorter, %.1f ms so far\n", (unsigned long long)w->ticket,
+                        w->entries.size(), w->text.len, sorter->msAppend);
+                    else
                     if (timing && A.outputBAM) fprintf(stderr, "[yaha] ticket %llu: %zu bytes of records compressed to %zu in %.1f ms (wait for the blocks included)\n",
                         (unsigned long long)w->ticket, w->text.len, w->packed.len, w->tPack);
                 }
@@ -660,6 +680,10 @@ int runQueries(Args &a, FILE *log)
         fprintf(log, "internal error: %llu of %llu batches were written -- the output is incomplete.\n", (unsigned long long)ticketsWritten.load(),
         (unsigned long long)ticketsIssued.load()); rcAll = 1; }
     // -obh / -obs: the end-of-file block, once, after the last batch of a run that got there
+    if (sorter && !stop && rcAll == 0) {
+        std::string serr;
+        if (sorter->finish(out, baiName, bamHeader(A, S->genome), S->genome.seqs.size(), bam, serr) != 0) { fprintf(log, "%s\n", serr.c_str()); rcAll = 1; }
+    } else
     if (A.outputBAM && !stop && rcAll == 0) { Text eof; bgzfEof(eof); bam.bytesWritten += eof.len; if (fwrite(eof.p, 1, eof.len, out) != eof.len) {
         fprintf(log, "Failure writing the output file.\n"); rcAll = 1; } }
     // The command line (csrc/main.cpp) leaves right after this function: it sets YAHA_FAST_EXIT and lets the process exit release the device memory and the
@@ -701,15 +725,16 @@ int runQueries(Args &a, FILE *log)
     if (!fastExit) for (int d = ngpu - 1; d >= 0; d--) if (ctx[d]) ygpu_destroy(ctx[d]);     // clones before their parents
     // (the batches -- a million small strings, the page-locked buffers -- go with the process as well: freeing them one by one was 0.3 s)
     if (fastExit) (void)new std::vector<BatchP>(std::move(pool.free));
-    if (fflush(out) != 0 || ferror(out)) { if (!stop) fprintf(log, "Failure writing the output file.\n"); rcAll = 1; }
-    if (out != stdout && fclose(out) != 0) { fprintf(log, "Failure closing the output file.\n"); rcAll = 1; }
+    if (sorter && rcAll != 0) dropSorted();                                    // (a sorted run that failed leaves neither FILE nor FILE.bai)
+    if (out && (fflush(out) != 0 || ferror(out))) { if (!stop) fprintf(log, "Failure writing the output file.\n"); rcAll = 1; }
+    if (out && out != stdout && fclose(out) != 0) { fprintf(log, "Failure closing the output file.\n"); rcAll = 1; }
     if (timing) fprintf(stderr, "[yaha] batches done %.1f ms after start, teardown %.1f ms\n", tDone - tEnter, now() - tDone);
     if (stats) {    // one line for scripts (bench.py): steady = reads written after the first batch / time from the first batch's write to the last one's
         const double steady = (nWritten > nFirst && tLastOut > tFirstOut) ? (nWritten - nFirst) / ((tLastOut - tFirstOut) * 1e-3) : 0.0;
         std::string per = "[";
         for (int k = 0; k < nDev; k++) { char t[32]; snprintf(t, sizeof t, "%s%llu", k ? ", " : "", (unsigned long long)devReads[k].load()); per += t; }
         per += "]";
-        char dstat[1664] = "";
+        char dstat[2048] = "";
         for (auto &T : tracks) { const size_t at = strlen(dstat); const BinnedTrack &t = *T.track;
             snprintf(dstat + at, sizeof dstat - at, T.statsFmt, (unsigned long long)t.nBins, (unsigned long long)t.devRecords, (unsigned long long)t.hostRecords,
                 (unsigned long long)t.sum());
@@ -727,6 +752,10 @@ int runQueries(Args &a, FILE *log)
                 "\"bam_blocks_stored\": %llu, \"bam_device_batches\": %llu, \"bam_host_batches\": %llu", (unsigned long long)bam.records.load(),
                 (unsigned long long)bam.bytesRaw.load(), (unsigned long long)bam.bytesWritten.load(), (unsigned long long)bam.blocks.load(),
                 (unsigned long long)bam.blocksStored.load(), (unsigned long long)bam.deviceBatches.load(), (unsigned long long)bam.hostBatches.load()); }
+        if (sorter) { const size_t at = strlen(dstat); const BamSortStats &bs = sorter->stats;
+            snprintf(dstat + at, sizeof dstat - at, ", \"bam_sorted_records\": %llu, \"bam_sort_device\": %d, \"bam_sort_segments\": %llu, \"bam_sort_windows\": %llu, "
+                "\"bam_sort_passes\": %llu, \"bai_bytes\": %llu", (unsigned long long)bs.records, bs.device ? 1 : 0, (unsigned long long)bs.segments,
+                (unsigned long long)bs.windows, (unsigned long long)bs.passes, (unsigned long long)bs.baiBytes); }
         fprintf(stderr, "[yaha] stats {\"reads\": %llu, \"contexts_up_ms\": %.1f, \"first_batch_written_ms\": %.1f, \"last_batch_written_ms\": %.1f, \"total_ms\": %.1f, "
             "\"steady_reads_per_s\": %.0f, \"cpus\": %d, \"formatters\": %d, \"parsers\": %d, \"gpus\": %d, \"ctx_per_gpu\": %d, \"ctx_left_out\": %d, "
             "\"reads_per_device\": %s, \"context_thread_ms_per_batch\": {\"wait_for_a_batch\": %.2f, \"upload\": %.2f, \"run\": %.2f, \"wait_for_filter_thread\": %.2f, "

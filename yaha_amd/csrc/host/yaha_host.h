@@ -75,6 +75,8 @@ struct Args {
     bool OQC = true; int OQCMinNonOverlap = -1, BPCost = 5, maxBPLog = 5; bool FBS = false; float FBS_PSLength = 0.90f, FBS_PSScore = 0.90f;
     int maxQueryLength = 32000; bool verbose = false, outputBlast8 = false, outputSAM = true, hardClip = true;
     bool outputBAM = false;                              // -obh / -obs: the SAM writer's records in BAM's layout, BGZF-compressed (bam.cpp); outputSAM stays set
+    // -obsort: the BAM in coordinate order with FILE.bai beside it, both written after the last alignment; -sortmem GB caps the record store (bam.cpp BamSorter)
+    bool bamSort = false, haveSortMem = false; int sortMemGB = 32;
     // extensions of this implementation (not in the reference CLI)
     int batchReads = 0; int device = 0; int gpus = 1; int ctxPerGpu = 3; bool cpuIndex = false; bool devicePostFilter = true;      // batchReads 0: batches of ~16 M bases
     // read-depth track: -ocov FILE (bedGraph), -covbin B (bases a bin), -covq Q (records below this mapping quality cover nothing)
@@ -155,7 +157,9 @@ void printClump(const Args &a, const Genome &g, const Read &r, const OutClump &o
 // The uncompressed header: "BAM\1", samHeader's text, the genome's sequences.  A record: printClump's record in BAM's layout, appended to out (false: the
 // clump spans two sequences and is dropped, as printClump drops it).
 std::string bamHeader(const Args &a, const Genome &g);
-bool bamRecord(const Args &a, const Genome &g, const Read &r, const OutClump &oc, int primaryCount, Text &out);
+// entry (may be null): what the sort and the index need of the record -- sequence, position, bytes (block_size's four included), end (exclusive), bin
+struct BamEntry { uint32_t ref, pos, len, end, bin; };
+bool bamRecord(const Args &a, const Genome &g, const Read &r, const OutClump &oc, int primaryCount, Text &out, BamEntry *entry = nullptr);
 struct BamStats { std::atomic<uint64_t> records{0}, bytesRaw{0}, bytesWritten{0}, blocks{0}, blocksStored{0}, deviceBatches{0}, hostBatches{0}; };
 // What a formatter thread compresses its batches with: a device handle of its own (ygpu_bgzf_*, looked up weakly as the tracks' entry points are), opened
 // when first needed and reopened when a batch outgrows it, or the host's encoder -- without the entry points, when no handle can be opened, with
@@ -170,6 +174,24 @@ struct BgzfPacker {
     struct Impl; Impl *impl;
 };
 void bgzfEof(Text &out);                                                  // appends the 28-byte end-of-file block
+// -obsort: the run's records, put into coordinate order and written with their index at the end of the run.  The writer thread appends every batch in ticket
+// order; finish() sorts -- stable, so equal keys keep print order --, writes the header's blocks (the host's encoder), the sorted stream's blocks window by
+// window, the end-of-file block, and FILE.bai (bai.cpp).  The store is a device handle (ygpu_bamsort_*, weak references) on device `device`; without the entry
+// points, with YAHA_HOST_BAMSORT=1 or when the handle cannot be opened it is host memory, ordered with std::stable_sort and compressed through BgzfPacker.  Both
+// are capped by capBytes.  A failure of an opened handle is an error of the run.
+struct BamSortStats { uint64_t records = 0, segments = 0, windows = 0, passes = 0, baiBytes = 0; bool device = false; };
+struct BamSorter {
+    BamSorter(int device, uint64_t capBytes); ~BamSorter(); BamSorter(const BamSorter &) = delete; BamSorter &operator=(const BamSorter &) = delete;
+    // 0, or an error code with err = a message (passing the cap: it names -sortmem)
+    int append(const char *bytes, size_t n, const BamEntry *entries, size_t nEntries, std::string &err);
+    int finish(FILE *out, const std::string &baiPath, const std::string &rawHeader, size_t nRefs, BamStats &st, std::string &err);
+    BamSortStats stats; double msAppend = 0;
+  private:
+    struct Impl; Impl *impl;
+};
+// The BAI of a sorted file (../bai_core.h): the entries in file order, the file offsets of the record blocks (coffs[nBlocks] = the end-of-file block's).
+void bamSortOrder(const BamEntry *entries, size_t n, uint32_t *perm);      // the host's ordering (stable): perm[j] = the record at sorted place j
+std::string baiBuild(const BamEntry *sorted, size_t n, size_t nRefs, const uint64_t *coffs, size_t nBlocks);
 
 // ---- the binned tracks: read depth (-ocov), the evidence track (-oev) and the allele pileup (-opu) (depth.cpp, events.cpp, pileup.cpp; ../*_core.h) --------
 // The host's array of a track, in the layout the device uses (one routine a kind, *_core.h): `channels` uint32 a bin, bin-major.  The formatter threads add the
