@@ -15,11 +15,18 @@ struct ChainClumpRec { uint32_t rs, fragOff, nFrags, region, seq, matched; };
 // six kernels start their chain of dependent fetches here) -- order == nullptr -- or, for the arena as the chain stage left it, through the rank table
 #define YD_ROOT_REC(A, r) ((A).order ? (A).clumps[(A).order[(r)]] : (A).clumps[(r)])
 
-#define YD_DEPTH 24
+// The split recursion's memory: two work buffers (a frame's list lives in the buffer of its depth's parity, with head-room for the extensions) and a save stack.
+// A frame that waits for a child keeps only the ops it will still read -- from its core's first item on -- packed on the save stack, and gets them back into its
+// work buffer when the child returns; so the depth costs a Frame a level, not a list buffer.  (A read of islands -- stretches of wordLen bases with a desert of
+// mismatches between them, chained into one clump -- splits once per island: the reference recurses as deep, AlignHelpers.c:374-557.)
+#define YD_SAVE_LISTS 4                                // the save stack, in list buffers: the waiting frames' ops are pieces of lists cut from one another
+// frames: every waiting frame has a core with a match of wordLen bases or more
+__host__ __device__ inline int alignDepthCap(int maxQ) { return maxQ / 4 + 64; }
 
 struct Frame {
     uint32_t sro; int sqo, eqo, refLen; int score, status, wS, wE; int start, len;
     int phase, minItem, maxItem, sQO, eQO; uint32_t sRO, eRO; int maxAGS;
+    int save;                                             // while the frame waits: where its ops from minItem on lie on the save stack
     int cSqo, cEqo, cRefLen; uint32_t cSro;               // the frame's fragment before the split rewrote it ("curFrag")
 };
 enum { PH_NONE = 0, PH_AFTER_HEAD = 1, PH_AFTER_TAIL = 2 };
@@ -35,7 +42,7 @@ struct AlignArgs {
 };
 
 // layout of one wave's scratch
-struct WaveMem { uint16_t *trace; uint32_t *tmpOps; int *gen; uint32_t *arena; Frame *frames; };
+struct WaveMem { uint16_t *trace; uint32_t *tmpOps; int *gen; uint32_t *arena; uint32_t *save; Frame *frames; };
 // traceRows: rows of 64 trace cells (>= maxQ + 2; more when -G / -MD allow gap fills whose strip does not fit that, see alignDims in stage_align.hip)
 __host__ __device__ inline size_t alignScratchBytes(int maxQ, int traceRows, int listCap, int genCap)
 {
@@ -43,8 +50,8 @@ __host__ __device__ inline size_t alignScratchBytes(int maxQ, int traceRows, int
     b += (size_t)traceRows * 64 * 2; b = (b + 255) & ~(size_t)255;
     b += (size_t)(2 * maxQ + 512) * 4; b = (b + 255) & ~(size_t)255;
     b += (size_t)3 * (genCap + 3) * 4; b = (b + 255) & ~(size_t)255;
-    b += (size_t)YD_DEPTH * listCap * 4; b = (b + 255) & ~(size_t)255;
-    b += (size_t)YD_DEPTH * sizeof(Frame); b = (b + 255) & ~(size_t)255;
+    b += (size_t)(2 + YD_SAVE_LISTS) * listCap * 4; b = (b + 255) & ~(size_t)255;
+    b += (size_t)alignDepthCap(maxQ) * sizeof(Frame); b = (b + 255) & ~(size_t)255;
     return b;
 }
 __device__ inline WaveMem carveScratch(uint8_t *p, int maxQ, int traceRows, int listCap, int genCap)
@@ -53,7 +60,7 @@ __device__ inline WaveMem carveScratch(uint8_t *p, int maxQ, int traceRows, int 
     m.trace = (uint16_t *)(p + b); b += (size_t)traceRows * 64 * 2; b = (b + 255) & ~(size_t)255;
     m.tmpOps = (uint32_t *)(p + b); b += (size_t)(2 * maxQ + 512) * 4; b = (b + 255) & ~(size_t)255;
     m.gen = (int *)(p + b); b += (size_t)3 * (genCap + 3) * 4; b = (b + 255) & ~(size_t)255;
-    m.arena = (uint32_t *)(p + b); b += (size_t)YD_DEPTH * listCap * 4; b = (b + 255) & ~(size_t)255;
+    m.arena = (uint32_t *)(p + b); m.save = m.arena + (size_t)2 * listCap; b += (size_t)(2 + YD_SAVE_LISTS) * listCap * 4; b = (b + 255) & ~(size_t)255;
     m.frames = (Frame *)(p + b);
     return m;
 }
@@ -99,7 +106,23 @@ struct Aligner {
         extCalls(0), extRows(0), extCells(0), gapCalls(0), gapRows(0), gapCells(0), perfect(0), touched(0), opsOut(0), splits(0), scored(0), rootRank(0), pushes(0)
     { S.ldsTrace = ldsTrace; S.trace = M.trace; S.traceRows = A.traceRows; S.tmpOps = M.tmpOps; S.tmpCap = 2 * A.maxQ + 512; S.gen = M.gen; S.genCap = A.genCap; S.err = &err; }
 
-    __device__ uint32_t *buf(int depth) const { return M.arena + (size_t)depth * A.listCap; }
+    __device__ uint32_t *buf(int depth) const { return M.arena + (size_t)(depth & 1) * A.listCap; }
+    // a frame goes to wait for a child: its ops from item minItem on, n of them, onto the save stack (false: the stack is full)
+    __device__ bool saveFrame(Frame &f, const uint32_t *b, int n, int &sp)
+    {
+        if ((long long)sp + n > (long long)YD_SAVE_LISTS * A.listCap) { err = YERR_ARENA; return false; }
+        for (int k = lane; k < n; k += 64) M.save[sp + k] = b[f.start + f.minItem + k];
+        f.save = sp; sp += n; return true;
+    }
+    // ... and comes back: item minItem at the front of its work buffer, the head-room of a fresh list on both sides
+    __device__ bool restoreFrame(Frame &f, uint32_t *b, int &sp)
+    {
+        const int n = f.phase == PH_AFTER_HEAD ? f.len - f.minItem : f.maxItem - f.minItem + 1;
+        if (A.front + n > A.listCap) { err = YERR_ARENA; return false; }
+        for (int k = lane; k < n; k += 64) b[A.front + k] = M.save[f.save + k];
+        __threadfence_block();
+        f.start = A.front - f.minItem; sp = f.save; return true;
+    }
     __device__ int gapCost(int len) const { return len > 0 ? -(P.GO + len * P.GE) : 0; }
     __device__ static uint32_t ero(uint32_t sro, int refLen) { return sro + (uint32_t)refLen - 1u; }
 
@@ -389,13 +412,13 @@ struct Aligner {
     // scoreClump / splitClump state machine on an aligned clump (frame 0)
     __device__ void finishRoot(Frame f)
     {
-        int depth = 0;
+        int depth = 0, sp = 0; const int depthCap = alignDepthCap(A.maxQ);      // sp: words on the save stack
         // per-frame results of the last scoreList
         int sm = -1, smm = 0, sg = 0, sl = 0, ss = 0;
         enum { ST_SCORE, ST_SPLIT_ENTER, ST_SPLIT_TAIL, ST_SPLIT_CORE, ST_RETURN } state = ST_SCORE;
         int guard = 0;
         while (!UNI_B(err != 0)) {
-            if (++guard > 100000) { err = YERR_DEPTH; break; }
+            if (++guard > 100000 + 64 * depthCap) { err = YERR_DEPTH; break; }
             state = (decltype(state))uni((int)state); depth = uni(depth);
             uint32_t *b = buf(depth);
             if (state == ST_SCORE) {
@@ -431,10 +454,11 @@ struct Aligner {
                 f.cSqo = f.sqo; f.cEqo = f.eqo; f.cSro = f.sro; f.cRefLen = f.refLen;
                 if (minItem != 0) {                                          // head remainder :463-495
                     if (hasMaxMatch(b, f.start, minItem)) {
-                        if (depth + 1 >= YD_DEPTH) { err = YERR_DEPTH; break; }
+                        if (depth + 1 >= depthCap) { err = YERR_DEPTH; break; }
                         uint32_t *cb = buf(depth + 1);
                         if (A.front + minItem > A.listCap) { err = YERR_ARENA; break; }
                         for (int k = lane; k < minItem; k += 64) cb[A.front + k] = b[f.start + k];
+                        if (!saveFrame(f, b, f.len - minItem, sp)) break;       // (the tail remainder and the core)
                         __threadfence_block();
                         Frame c; c.status = f.status & stReversed; c.sqo = f.cSqo; c.eqo = (sQO - 1) & 0xFFFF; c.sro = f.cSro;
                             c.refLen = (int)((1u + (sRO - 1u) - f.cSro) & 0xFFFFu);
@@ -449,10 +473,11 @@ struct Aligner {
                 if (f.maxItem != n - 1) {
                     const int t0 = f.maxItem + 1, tl = n - t0;
                     if (hasMaxMatch(b, f.start + t0, tl)) {
-                        if (depth + 1 >= YD_DEPTH) { err = YERR_DEPTH; break; }
+                        if (depth + 1 >= depthCap) { err = YERR_DEPTH; break; }
                         uint32_t *cb = buf(depth + 1);
                         if (A.front + tl > A.listCap) { err = YERR_ARENA; break; }
                         for (int k = lane; k < tl; k += 64) cb[A.front + k] = b[f.start + t0 + k];
+                        if (!saveFrame(f, b, f.maxItem - f.minItem + 1, sp)) break;      // (the core)
                         __threadfence_block();
                         Frame c; c.status = f.status & stReversed; c.sqo = (f.eQO + 1) & 0xFFFF; c.eqo = f.cEqo; c.sro = f.eRO + 1u;
                         c.refLen = (int)((1u + ero(f.cSro, f.cRefLen) - (f.eRO + 1u)) & 0xFFFFu);
@@ -477,6 +502,7 @@ struct Aligner {
                 break; }
             if (f.status & stScored) { f.status |= stSplit | stAligned; emit(f, b, sm, smm, sg, sl, ss); }
             depth--; f = M.frames[depth];
+            if (!restoreFrame(f, buf(depth), sp)) break;
             if (f.phase == PH_AFTER_HEAD) state = ST_SPLIT_TAIL; else state = ST_SPLIT_CORE;
         }
     }

@@ -68,6 +68,8 @@ int stageChain(ygpu_ctx *ctx)
         HIPCHK(hipMemsetAsync(ctx->clumps.p, 0xFF, sizeof(ChainClumpRec) * (uint64_t)clumpCap, ctx->stream));        // invalid until written
         HIPCHK(hipMemsetAsync(ctx->regionCount.p, 0, 4ull * (R + 1), ctx->stream));
         HIPCHK(hipMemsetAsync(ctx->errFlag.p, 0, 4, ctx->stream));
+        // (only this stage's kernels count the clumps formed: an attempt that overflowed has counted those it did form)
+        HIPCHK(hipMemsetAsync(&ctx->ctr.as<DevCounters>()->v[C_FORMED], 0, sizeof(unsigned long long), ctx->stream));
         ChainArgs A; A.P = ctx->P; A.B = B; A.frags = ctx->frags.as<DevFrag>(); A.regStart = ctx->regStart.as<uint32_t>(); A.nRegions = R;
         A.multiList = ctx->multiList.as<uint32_t>(); A.nMulti = ctx->nMulti; A.queueHead = cnt + CNT_QCHAIN;
         A.scratch = ctx->scratchChain.as<uint8_t>(); A.scratchPerWave = per; A.maxN = maxN; A.maxQ = ctx->maxQ;
