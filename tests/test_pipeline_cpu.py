@@ -145,6 +145,52 @@ def test_the_filter_thread_overlaps_the_next_batch(exes, work, index11, san):
     assert len(b) < len(g) and g.startswith(b) and (b.endswith("\n") or b == "")
 
 
+SIDE = [("-ocov", "cov"), ("-oev", "ev"), ("-opu", "pu"), ("-obp", "bp"), ("-oid", "id")]
+
+
+def test_all_outputs_in_one_run(exes, work, index11, tmp_path):
+    """Every side output beside the main one in ONE run, under ThreadSanitizer, over four contexts on two devices with three formatter threads (the run driver
+    knows the outputs as a list, SideOutput / RecordSink in host/yaha_host.h: each keeps a slot in every recycled batch object).  Each side file equals,
+    byte for byte, the file of a run with that option alone; the SAM is the golden; the sorted BAM decodes to what a run without a side option gives (the
+    header's @PG names the options, so it is left out of that comparison, as strip_pg leaves it out of every SAM's) and its index fits it.  The same when the
+    reads of more than three clumps come back unfiltered and the formatters do those.  A run that fails with -obsort and every side option exits with code 1
+    and leaves no file at all."""
+    import bai_oracle as ba
+    import bam_oracle as bo
+    base = ["-x", index11, "-q", os.path.join(work, "rsv.fa"), "-gpus", "2", "-ctx", "2", "-batch", "29", "-t", "3"]
+
+    def go(tag, main, opts, env=None, rc=0):
+        d = tmp_path / tag; d.mkdir()
+        out = str(d / ("out.bam" if main == "sorted" else "out.sam"))
+        args = base + (["-obs", out, "-obsort"] if main == "sorted" else ["-osh", out]) + [x for o, n in opts for x in (o, str(d / n))]
+        if ("-oid", "id") in opts:
+            args += ["-idmin", "1"]                                           # (no allele of this read set is carried by two records: the default would leave the file empty)
+        p = _run(exes["tsan"], args, env=dict({"YTEST_DEVICES": "2", "YAHA_CPUS": "6"}, **(env or {})))
+        _clean(p)
+        assert p.returncode == rc, (tag, p.stderr.decode()[-2000:])
+        return d, p
+
+    def decoded(d):
+        data = (d / "out.bam").read_bytes()
+        ba.check_contract(data, (d / "out.bam.bai").read_bytes())
+        return strip_pg(bo.bam_to_sam(bo.read_file(data)[0])[0])
+
+    alone = {n: (go("alone_" + n, "sam", [(o, n)])[0] / n).read_bytes() for o, n in SIDE}
+    assert all(alone.values())                                                # (none of the five files is empty on this read set)
+    plain = decoded(go("sorted_plain", "sorted", [])[0])
+    for tag, main, env in (("all_sam", "sam", None), ("all_sorted", "sorted", None), ("all_raw", "sam", {"YTEST_RAW_ABOVE": "3"})):
+        d, _p = go(tag, main, SIDE, env=env)
+        for _o, n in SIDE:
+            assert (d / n).read_bytes() == alone[n], (tag, n)
+        if main == "sam":
+            assert strip_pg((d / "out.sam").read_text()) == golden_lines("rsv_default"), tag
+        else:
+            assert decoded(d) == plain
+    d, p = go("failing", "sorted", SIDE, env={"YTEST_FAIL_RUN": "3"}, rc=1)
+    assert "hot path failed" in p.stderr.decode() and "stopping" in p.stderr.decode()
+    assert os.listdir(str(d)) == []                                          # neither FILE nor FILE.bai, and no side file
+
+
 def test_no_such_device(exes, work, index11):
     p = _run(exes["asan"], ["-x", index11, "-q", os.path.join(work, "r1k.fa"), "-osh", "stdout", "-gpus", "2"], env={"YTEST_DEVICES": "1"})
     _clean(p)

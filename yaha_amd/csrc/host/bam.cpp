@@ -343,4 +343,92 @@ int BamSorter::finish(FILE *out, const std::string &baiPath, const std::string &
 }
 
 void bgzfEof(Text &out) { ybgzf::putEof((uint8_t *)out.room(ybgzf::EOF_BYTES)); out.len += ybgzf::EOF_BYTES; }
+
+// ---- the main output as BAM (RecordSink, yaha_host.h) ---------------------------------------------------------------------------------------------------------
+namespace {
+// -obh / -obs: the header is BGZF blocks of its own from the host's encoder; every batch's records are compressed by the thread that formats them, with a packer
+// of its own, and the end-of-file block follows the last batch of a run that got there
+struct BamSink : RecordSink {
+    BamStats bam; std::vector<std::unique_ptr<BgzfPacker>> packers;
+    bool begin(const Args &a, const Genome &g, const std::string &, int nFormatters, FILE *log) override
+    {
+        for (int i = 0; i < nFormatters; i++) packers.emplace_back(new BgzfPacker);
+        const std::string raw = bamHeader(a, g); Text packed; BgzfPacker hostPacker; hostPacker.packHost(raw.data(), raw.size(), packed, bam);
+        if (fwrite(packed.p, 1, packed.len, out) != packed.len) { fprintf(log, "Failure writing the output file.\n"); return false; }
+        return true;
+    }
+    bool pack(SinkBatch &b, int formatter, bool stopped, std::string &err) override
+    {
+        std::string perr; b.packed.clear();                                // (a batch without records is no block: an empty one would read as the end of the file)
+        const int rc = stopped ? 0 : packers[formatter]->pack(b.dev, b.text.p, b.text.len, b.packed, bam, perr);
+        bam.records += b.records;
+        if (rc != 0) { char m[640]; snprintf(m, sizeof m, "BGZF compression on device %d failed (%d): %s", b.dev, rc, perr.c_str()); err = m; }
+        return rc == 0;
+    }
+    bool write(SinkBatch &b, std::string &err) override { return writeBytes(b.packed, err); }
+    void timingLine(const SinkBatch &b, uint64_t ticket) const override
+    {
+        fprintf(stderr, "[yaha] ticket %llu: %zu bytes of records compressed to %zu in %.1f ms (wait for the blocks included)\n", (unsigned long long)ticket, b.text.len,
+            b.packed.len,
+            b.tPack);
+    }
+    bool finish(FILE *log) override
+    {
+        Text eof; bgzfEof(eof); bam.bytesWritten += eof.len;
+        if (fwrite(eof.p, 1, eof.len, out) != eof.len) { fprintf(log, "Failure writing the output file.\n"); return false; }
+        return true;
+    }
+    void stats(std::string &line) const override
+    {
+        char t[512]; snprintf(t, sizeof t, ", \"bam_records\": %llu, \"bam_bytes_raw\": %llu, \"bam_bytes_written\": %llu, \"bam_blocks\": %llu, "
+            "\"bam_blocks_stored\": %llu, \"bam_device_batches\": %llu, \"bam_host_batches\": %llu", (unsigned long long)bam.records.load(),
+            (unsigned long long)bam.bytesRaw.load(), (unsigned long long)bam.bytesWritten.load(), (unsigned long long)bam.blocks.load(),
+            (unsigned long long)bam.blocksStored.load(), (unsigned long long)bam.deviceBatches.load(), (unsigned long long)bam.hostBatches.load());
+        line += t;
+    }
+};
+// -obsort: nothing is written before the last alignment -- the raw records travel to the writer thread and into the sorter (a store on device -device, or the
+// host's), appended in ticket order, which is what makes equal keys keep print order; the sorter writes the header's blocks, the sorted stream's and FILE.bai at
+// the end.  A failed run leaves neither file behind.
+struct SortedBamSink : BamSink {
+    std::unique_ptr<BamSorter> sorter; const Args *args = nullptr; const Genome *genome = nullptr;
+    bool begin(const Args &a, const Genome &g, const std::string &, int, FILE *log) override
+    {
+        args = &a; genome = &g;
+        for (auto &sq : g.seqs) if (sq.length > (1u << 29)) {
+            fprintf(log, "-obsort: sequence %s has %u bases; BAI indexes sequences of up to 2^29 = 536870912 bases.\n", sq.name.c_str(), sq.length); abandon(); return false; }
+        uint64_t capBytes = (uint64_t)a.sortMemGB << 30;
+        if (const char *e = getenv("YAHA_SORTMEM_BYTES")) { const long long v = atoll(e); if (v > 0) capBytes = (uint64_t)v; }      // (byte-granular, for tests)
+        sorter.reset(new BamSorter(a.device, capBytes)); return true;
+    }
+    std::vector<BamEntry> *entries(SinkBatch &b) const override { return &b.entries; }
+    bool pack(SinkBatch &b, int, bool, std::string &) override { bam.records += b.records; return true; }
+    bool write(SinkBatch &b, std::string &err) override { return sorter->append(b.text.p, b.text.len, b.entries.data(), b.entries.size(), err) == 0; }
+    void timingLine(const SinkBatch &b, uint64_t ticket) const override
+    {
+        fprintf(stderr, "[yaha] ticket %llu: %zu records (%zu bytes) appended to the sorter, %.1f ms so far\n", (unsigned long long)ticket, b.entries.size(), b.text.len,
+            sorter->msAppend);
+    }
+    bool finish(FILE *log) override
+    {
+        std::string serr;
+        if (sorter->finish(out, path + ".bai", bamHeader(*args, *genome), genome->seqs.size(), bam, serr) != 0) { fprintf(log, "%s\n", serr.c_str()); return false; }
+        return true;
+    }
+    void abandon() override { if (out != stdout) { fclose(out); out = nullptr; } remove(path.c_str()); remove((path + ".bai").c_str()); }
+    void stats(std::string &line) const override
+    {
+        BamSink::stats(line); const BamSortStats &bs = sorter->stats;
+        char t[384]; snprintf(t, sizeof t, ", \"bam_sorted_records\": %llu, \"bam_sort_device\": %d, \"bam_sort_segments\": %llu, \"bam_sort_windows\": %llu, "
+            "\"bam_sort_passes\": %llu, \"bai_bytes\": %llu", (unsigned long long)bs.records, bs.device ? 1 : 0, (unsigned long long)bs.segments,
+            (unsigned long long)bs.windows, (unsigned long long)bs.passes, (unsigned long long)bs.baiBytes);
+        line += t;
+    }
+};
+}  // namespace
+
+std::unique_ptr<RecordSink> makeRecordSink(const Args &a)
+{
+    return std::unique_ptr<RecordSink>(a.bamSort ? new SortedBamSink : a.outputBAM ? new BamSink : new RecordSink);
+}
 }  // namespace yaha

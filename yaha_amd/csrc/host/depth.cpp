@@ -7,6 +7,7 @@
 // as when the library refuses to enable the stage -- the host counts every record itself.
 #include "yaha_host.h"
 #include <algorithm>
+#include <chrono>
 
 extern "C" {
 __attribute__((weak)) int ygpu_depth_enable(ygpu_ctx *ctx, const ygpu_depth_params *p);
@@ -17,14 +18,51 @@ __attribute__((weak)) int ygpu_depth_collect(ygpu_ctx *ctx, uint32_t *bins, uint
 namespace yaha {
 
 // ---- what the tracks share ------------------------------------------------------------------------------------------------------------------------------
-bool BinnedTrack::init(const Genome &g, int binBases, int minQ, std::string &err)
+bool BinnedTrack::init(const Genome &g, const std::string &path, int binBases, int minQ, int nImages, int nContexts, std::string &err)
 {
-    bin = (uint32_t)binBases; minMapq = (uint32_t)minQ;
-    seqStart.clear(); seqLength.clear(); for (auto &sq : g.seqs) { seqStart.push_back(sq.start); seqLength.push_back(sq.length); }
-    binBase.assign(seqStart.size() + 1, 0);
-    if (binBases < 1 || !ydepth::layoutBins(seqLength.data(), (uint32_t)seqLength.size(), bin, binBase.data(), &nBins)) {
+    genome = &g; file = path; bin = (uint32_t)binBases; minMapq = (uint32_t)minQ;
+    ctxs.assign((size_t)nContexts, CtxAt{nullptr, 0, 0, 0}); feeder = std::vector<std::atomic<int>>((size_t)nImages); for (auto &x : feeder) x = 0;
+    seqs.set(g); binBase.assign(seqs.start.size() + 1, 0);
+    if (binBases < 1 || !ydepth::layoutBins(seqs.length.data(), (uint32_t)seqs.length.size(), bin, binBase.data(), &nBins)) {
         err = std::string(names.binOpt) + ": the bins do not fit 32 bits"; return false; }
     return allocate(err);
+}
+
+int BinnedTrack::enable(const CtxAt &at)
+{
+    if (getenv(names.hostSwitch) != nullptr) return YGPU_ENODEV;
+    // (no room for the array beside the image and the arenas stops the run, with the sizes: a host array would hide that the device is full; larger bins are the way out)
+    const int rc = deviceEnable(at.ctx); if (rc == 0) ctxs[at.index] = at;
+    return rc;
+}
+
+int BinnedTrack::beforeFilter(const CtxAt &at, size_t)
+{
+    if (feeder[at.image].load(std::memory_order_relaxed) == 0) { int none = 0; feeder[at.image].compare_exchange_strong(none, at.index + 1); }
+    return 0;
+}
+
+// every image's array added to the host's, the file written after the last alignment
+bool BinnedTrack::finish(FILE *mainOut, FILE *log, bool timing)
+{
+    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    std::string terr; bool ok = true; std::vector<ygpu_ctx *> feedCtx; std::vector<int> feedDev;
+    for (auto &x : feeder) if (const int c1 = x.load()) { feedCtx.push_back(ctxs[c1 - 1].ctx); feedDev.push_back(ctxs[c1 - 1].device); }
+    const double m0 = now();
+    int failed = -1; const int rc = mergeDevices(feedCtx.data(), (int)feedCtx.size(), *genome, &failed, terr);
+    const double m1 = now();
+    if (rc != 0) { fprintf(log, "%s: collecting the %s array of device %d failed (%d): %s\n", names.fileOpt, names.array, failed >= 0 ? feedDev[failed] : -1, rc, terr.c_str());
+        ok = false; }
+    if (fflush(mainOut) != 0) ok = false;
+    if (ok && !write(file.c_str(), *genome, terr)) { fprintf(log, "%s\n", terr.c_str()); ok = false; }
+    if (timing) fprintf(stderr, "[yaha] %s: devices merged in %.1f ms%s, file written in %.1f ms\n", names.fileOpt, m1 - m0, mergeNote().c_str(), now() - m1);
+    return ok;
+}
+
+void BinnedTrack::stats(std::string &line) const
+{
+    char t[512]; snprintf(t, sizeof t, names.statsFmt, (unsigned long long)nBins, (unsigned long long)devRecords, (unsigned long long)hostRecords, (unsigned long long)sum());
+    line += t; line += extraStats();
 }
 
 bool BinnedTrack::allocate(std::string &err)
@@ -77,9 +115,14 @@ bool BinnedTrack::write(const char *path, const Genome &g, std::string &err) con
 }
 
 // ---- read depth -----------------------------------------------------------------------------------------------------------------------------------------
-DepthTrack::DepthTrack() : BinnedTrack({"-covbin", "-ocov", "coverage", "depth"}, 1, ygpu_depth_enable != nullptr, ygpu_depth_size, ygpu_depth_collect) {}
+DepthTrack::DepthTrack() : BinnedTrack({"-covbin", "-ocov", "coverage", "depth", "YAHA_HOST_DEPTH",
+    ", \"depth_bins\": %llu, \"depth_device_records\": %llu, \"depth_host_records\": %llu, \"depth_covered_bases\": %llu"}, 1, ygpu_depth_enable != nullptr, ygpu_depth_size,
+    ygpu_depth_collect) {}
 
-void DepthTrack::add(const OutClump &oc, const Read &)
+bool DepthTrack::setup(const Args &a, const Genome &g, int nImages, int nContexts, std::string &err) { return init(g, a.covFileName, a.covBin, a.covMinQ, nImages, nContexts, err);
+    }
+
+void DepthTrack::add(const OutClump &oc, const Read &, Slot *)
 {
     uint32_t *const c = data; const uint64_t n = nBins;
     countRecord(ydepth::walkClump(layout(), oc.c, oc.ops, oc.mapQuality, [c, n](uint32_t b, uint32_t k) { if (b < n) __atomic_fetch_add(c + b, k, __ATOMIC_RELAXED); }, nullptr));
@@ -88,7 +131,7 @@ void DepthTrack::add(const OutClump &oc, const Read &)
 int DepthTrack::deviceEnable(ygpu_ctx *ctx) const
 {
     if (!deviceEntryPoints()) return YGPU_ENODEV;
-    ygpu_depth_params p; p.bin = bin; p.min_mapq = minMapq; p.n_seqs = (uint32_t)seqStart.size(); p.seq_start = seqStart.data(); p.seq_length = seqLength.data();
+    ygpu_depth_params p; p.bin = bin; p.min_mapq = minMapq; seqs.into(p);
     return ygpu_depth_enable(ctx, &p);
 }
 
@@ -98,7 +141,7 @@ bool DepthTrack::writeLines(FILE *f, const Genome &g) const
 {
     bool ok = true;
     for (size_t s = 0; s < g.seqs.size() && ok; s++) {
-        const char *name = g.seqs[s].name.c_str(); const uint32_t len = seqLength[s]; const uint32_t *c = data + binBase[s];
+        const char *name = g.seqs[s].name.c_str(); const uint32_t len = seqs.length[s]; const uint32_t *c = data + binBase[s];
         if (bin == 1) {
             for (uint32_t i = 0; i < len && ok;) {
                 if (!c[i]) { i++; continue; }

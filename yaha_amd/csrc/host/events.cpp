@@ -17,11 +17,16 @@ __attribute__((weak)) int ygpu_events_collect(ygpu_ctx *ctx, uint32_t *counts, u
 
 namespace yaha {
 
-EventsTrack::EventsTrack(int minClipBases)
-    : BinnedTrack({"-evbin", "-oev", "evidence", "events"}, (uint32_t)yevents::NCH, ygpu_events_enable != nullptr, ygpu_events_size, ygpu_events_collect),
-      minClip((uint32_t)minClipBases) {}
+EventsTrack::EventsTrack() : BinnedTrack({"-evbin", "-oev", "evidence", "events", "YAHA_HOST_EVENTS",
+    ", \"events_bins\": %llu, \"events_device_records\": %llu, \"events_host_records\": %llu, \"events_counted\": %llu"}, (uint32_t)yevents::NCH, ygpu_events_enable != nullptr,
+    ygpu_events_size, ygpu_events_collect) {}
 
-void EventsTrack::add(const OutClump &oc, const Read &r)
+bool EventsTrack::setup(const Args &a, const Genome &g, int nImages, int nContexts, std::string &err)
+{
+    minClip = (uint32_t)a.evMinClip; return init(g, a.evFileName, a.evBin, a.evMinQ, nImages, nContexts, err);
+}
+
+void EventsTrack::add(const OutClump &oc, const Read &r, Slot *)
 {
     uint32_t *const e = data; const uint64_t n = nBins;
     countRecord(yevents::walkClump(layout(), minClip, oc.c, oc.ops, (uint32_t)r.len(), oc.mapQuality,
@@ -31,8 +36,7 @@ void EventsTrack::add(const OutClump &oc, const Read &r)
 int EventsTrack::deviceEnable(ygpu_ctx *ctx) const
 {
     if (!deviceEntryPoints()) return YGPU_ENODEV;
-    ygpu_events_params p; p.bin = bin; p.min_mapq = minMapq; p.min_clip = minClip; p.n_seqs = (uint32_t)seqStart.size(); p.seq_start = seqStart.data();
-        p.seq_length = seqLength.data();
+    ygpu_events_params p; p.bin = bin; p.min_mapq = minMapq; p.min_clip = minClip; seqs.into(p);
     return ygpu_events_enable(ctx, &p);
 }
 
@@ -42,7 +46,7 @@ bool EventsTrack::writeLines(FILE *f, const Genome &g) const
 {
     bool ok = fputs("#chrom\tstart\tend\tmismatch\tdeleted\tinsertion\tclip_left\tclip_right\n", f) >= 0;
     for (size_t s = 0; s < g.seqs.size() && ok; s++) {
-        const char *name = g.seqs[s].name.c_str(); const uint32_t len = seqLength[s], nb = binBase[s + 1] - binBase[s];
+        const char *name = g.seqs[s].name.c_str(); const uint32_t len = seqs.length[s], nb = binBase[s + 1] - binBase[s];
         const uint32_t *c = data + (size_t)binBase[s] * yevents::NCH;
         for (uint32_t b = 0; b < nb && ok; b++, c += yevents::NCH) if (c[0] | c[1] | c[2] | c[3] | c[4]) {
             const uint64_t lo = (uint64_t)b * bin, hi = std::min<uint64_t>(lo + bin, len);

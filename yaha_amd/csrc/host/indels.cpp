@@ -23,26 +23,29 @@ namespace yaha {
 static inline yindel::Key coreKey(const IndelKey &k) { yindel::Key c; c.w0 = k.w0; c.w1 = k.w1; c.w2 = k.w2; return c; }
 bool IndelKeyLess::operator()(const IndelKey &a, const IndelKey &b) const { return yindel::keyLess(coreKey(a), coreKey(b)); }
 
-bool IndelTrack::init(const Genome &g, int minQ, int minLength, int minRecords, std::string &err)
+bool IndelTrack::setup(const Args &a, const Genome &g, int, int nContexts, std::string &err)
 {
-    minMapq = (uint32_t)minQ; minLen = (uint32_t)minLength; minCount = (uint32_t)minRecords;
-    seqStart.clear(); seqLength.clear(); for (auto &sq : g.seqs) { seqStart.push_back(sq.start); seqLength.push_back(sq.length); }
-    binBase.assign(seqStart.size() + 1, 0);
-    if (!ydepth::layoutBins(seqLength.data(), (uint32_t)seqLength.size(), 1, binBase.data(), &nSlots)) { err = "-oid: the reference bases do not fit 32 bits"; return false; }
+    genome = &g; file = a.idFileName; minMapq = (uint32_t)a.idMinQ; minLen = (uint32_t)a.idLen; minCount = (uint32_t)a.idMin;
+    enabled.assign((size_t)nContexts, CtxAt{nullptr, 0, 0, 0});
+    capacity = yindel::tableCapacity(a.batchReads > 0 ? std::min<uint64_t>((uint64_t)a.batchReads * (uint64_t)std::max(1, a.maxQueryLength), (uint64_t)16 << 20)
+        : (uint64_t)16 << 20);
+    seqs.set(g); binBase.assign(seqs.start.size() + 1, 0);
+    if (!ydepth::layoutBins(seqs.length.data(), (uint32_t)seqs.length.size(), 1, binBase.data(), &nSlots)) { err = "-oid: the reference bases do not fit 32 bits"; return false; }
     return true;
 }
 
-void IndelTrack::add(const OutClump &oc, const Read &r, Local &local) const
+void IndelTrack::add(const OutClump &oc, const Read &r, Slot *s)
 {
-    const ydepth::Layout L{seqStart.data(), seqLength.data(), binBase.data(), (uint32_t)seqStart.size(), 1u, minMapq};
-    std::vector<IndelKey> &keys = local.keys;
+    const ydepth::Layout L{seqs.start.data(), seqs.length.data(), binBase.data(), (uint32_t)seqs.start.size(), 1u, minMapq};
+    Local &local = *static_cast<Local *>(s); std::vector<IndelKey> &keys = local.keys;
     const int g = yindel::walkClump(L, oc.c, oc.ops, r.fwdCodes.data(), (uint32_t)r.fwdCodes.size(), (oc.status & 0x01) != 0, oc.mapQuality, minLen,
         [&keys](const yindel::Key &k) { keys.push_back(IndelKey{k.w0, k.w1, k.w2}); });
     if (g == ydepth::COUNTED) local.records++; else if (g == ydepth::SKIPPED_MAPQ) local.skipped++; else local.dropped++;
 }
 
-void IndelTrack::merge(Local &local)
+void IndelTrack::endBatch(Slot *s)
 {
+    Local &local = *static_cast<Local *>(s);
     if (local.keys.empty() && !local.records && !local.skipped && !local.dropped) return;
     std::sort(local.keys.begin(), local.keys.end(), IndelKeyLess());       // (equal keys side by side: one look-up each)
     {
@@ -58,15 +61,22 @@ void IndelTrack::merge(Local &local)
 
 bool IndelTrack::deviceEntryPoints() { return ygpu_indels_enable != nullptr && ygpu_indels_size != nullptr && ygpu_indels_collect != nullptr; }
 
-int IndelTrack::deviceEnable(ygpu_ctx *ctx, uint64_t capacity) const
+int IndelTrack::enable(const CtxAt &at)
 {
-    if (!deviceEntryPoints()) return YGPU_ENODEV;
+    if (!deviceEntryPoints() || getenv("YAHA_HOST_INDELS") != nullptr) return YGPU_ENODEV;
     ygpu_indel_params p; memset(&p, 0, sizeof p);
-    p.min_mapq = minMapq; p.min_length = minLen; p.n_seqs = (uint32_t)seqStart.size(); p.seq_start = seqStart.data(); p.seq_length = seqLength.data(); p.capacity = capacity;
-    return ygpu_indels_enable(ctx, &p);
+    p.min_mapq = minMapq; p.min_length = minLen; seqs.into(p); p.capacity = capacity;
+    const int rc = ygpu_indels_enable(at.ctx, &p); if (rc == 0) enabled[at.index] = at;
+    return rc;
 }
 
-int IndelTrack::deviceSize(ygpu_ctx *ctx, uint64_t *used) const { return deviceEntryPoints() ? ygpu_indels_size(ctx, used) : YGPU_ENODEV; }
+int IndelTrack::drainAbove(ygpu_ctx *ctx, uint64_t more, uint64_t limit)
+{
+    uint64_t used = 0; std::string err; const int rc = ygpu_indels_size(ctx, &used);
+    return rc == 0 && used && used + more > limit ? deviceDrain(ctx, true, err) : rc;
+}
+int IndelTrack::beforeFilter(const CtxAt &at, size_t batchBases) { return drainAbove(at.ctx, batchBases / 2, capacity / 2); }
+int IndelTrack::afterFilter(const CtxAt &at, Slot *) { return drainAbove(at.ctx, 0, capacity / 4); }
 
 int IndelTrack::deviceDrain(ygpu_ctx *ctx, bool duringRun, std::string &err)
 {
@@ -81,6 +91,28 @@ int IndelTrack::deviceDrain(ygpu_ctx *ctx, bool duringRun, std::string &err)
     devRecords += st[0]; devSkipped += st[1]; devDropped += st[2]; devEvents += st[3]; devHandedBack += st[4]; devLost += st[5];
     if (duringRun) drains++;
     return 0;
+}
+
+// the end of the run: what every enabled context's table still holds, then the file
+bool IndelTrack::finish(FILE *mainOut, FILE *log, bool)
+{
+    std::string ierr; bool ok = true;
+    for (const CtxAt &at : enabled) if (at.ctx && ok) {
+        const int rc = deviceDrain(at.ctx, false, ierr);
+        if (rc != 0) { fprintf(log, "-oid: collecting the indel table of context %d failed (%d): %s\n", at.index, rc, ierr.c_str()); ok = false; }
+    }
+    if (devLost) { fprintf(log, "-oid: %llu indel events found no entry in a device table -- the file would be incomplete.\n", (unsigned long long)devLost); ok = false; }
+    if (fflush(mainOut) != 0) ok = false;
+    if (ok && !write(file.c_str(), *genome, ierr)) { fprintf(log, "%s\n", ierr.c_str()); ok = false; }
+    return ok;
+}
+
+void IndelTrack::stats(std::string &line) const
+{
+    char t[512]; snprintf(t, sizeof t, ", \"indel_device_records\": %llu, \"indel_host_records\": %llu, \"indel_events\": %llu, \"indel_alleles\": %llu, "
+        "\"indel_lines\": %llu, \"indel_drains\": %llu, \"indel_lost\": %llu", (unsigned long long)devRecords, (unsigned long long)hostRecords,
+        (unsigned long long)(devEvents + hostEvents), (unsigned long long)alleles.size(), (unsigned long long)nLines, (unsigned long long)drains, (unsigned long long)devLost);
+    line += t;
 }
 
 // One line per allele at least minCount records carry, in the map's order: name, position (1-based within the sequence: a deletion's first deleted base, an

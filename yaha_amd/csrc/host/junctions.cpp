@@ -17,47 +17,68 @@ __attribute__((weak)) int ygpu_junctions_collect(ygpu_ctx *ctx, ygpu_junction *o
 
 namespace yaha {
 
-void JunctionTrack::init(const Genome &g, int minQ, int w)
+bool JunctionTrack::setup(const Args &a, const Genome &g, int, int, std::string &)
 {
-    minMapq = (uint32_t)minQ; window = (uint32_t)w;
-    seqStart.clear(); seqLength.clear(); for (auto &sq : g.seqs) { seqStart.push_back(sq.start); seqLength.push_back(sq.length); }
+    genome = &g; file = a.bpFileName; minMapq = (uint32_t)a.bpMinQ; window = (uint32_t)a.bpWindow; seqs.set(g); return true;
 }
 
-uint32_t JunctionTrack::addRead(const OutClump *recs, uint32_t n, int qlen, uint32_t read, std::vector<ygpu_junction> &out, uint32_t *skipped) const
+void JunctionTrack::beginBatch(Slot *s, bool onDevice) const
 {
-    if (skipped) *skipped = 0;
-    if (n == 0) return 0;
-    const ydepth::Layout L = yjunc::layout(seqStart.data(), seqLength.data(), (uint32_t)seqStart.size(), minMapq);
-    return yjunc::readJunctions(L, n, (uint32_t)qlen, read,
+    Batch &b = *static_cast<Batch *>(s); b.host.clear(); b.hostReads = b.hostSkipped = 0;
+    if (!onDevice) { b.dev.clear(); memset(b.devStats, 0, sizeof b.devStats); }
+}
+
+void JunctionTrack::endRead(const OutClump *recs, uint32_t n, const Read &r, uint32_t read, Slot *s) const
+{
+    if (n == 0) return;
+    Batch &b = *static_cast<Batch *>(s); std::vector<ygpu_junction> &out = b.host; uint32_t skipped = 0;      // (skipped: records gated by MAPQ alone)
+    const ydepth::Layout L = yjunc::layout(seqs.start.data(), seqs.length.data(), (uint32_t)seqs.start.size(), minMapq);
+    if (yjunc::readJunctions(L, n, (uint32_t)r.len(), read,
         [recs](uint32_t k, const ygpu_clump **c, uint32_t *status, uint32_t *mq) { *c = &recs[k].c; *status = recs[k].status; *mq = recs[k].mapQuality; },
-        [&out](const ygpu_junction &j) { out.push_back(j); }, skipped);
+        [&out](const ygpu_junction &j) { out.push_back(j); }, &skipped)) b.hostReads++;
+    b.hostSkipped += skipped;
 }
 
-void JunctionTrack::addBatch(const ygpu_junction *dev, size_t nDev, const uint64_t devStats[4], const std::vector<ygpu_junction> &host, uint64_t hostReadsB, uint64_t hostSkippedB)
+void JunctionTrack::written(Slot *s)
 {
     // (a read's junctions come from one side only, in ordinal order: merging by read keeps them together)
-    const size_t at = all.size(); all.resize(at + nDev + host.size());
-    std::merge(dev, dev + nDev, host.begin(), host.end(), all.begin() + at, [](const ygpu_junction &a, const ygpu_junction &b) { return a.read < b.read; });
-    if (devStats) { devReads += devStats[0]; devSkipped += devStats[2]; devHandedBack += devStats[3]; }
-    hostReads += hostReadsB; hostSkipped += hostSkippedB;
+    const Batch &b = *static_cast<Batch *>(s); const size_t at = all.size(); all.resize(at + b.dev.size() + b.host.size());
+    std::merge(b.dev.begin(), b.dev.end(), b.host.begin(), b.host.end(), all.begin() + at, [](const ygpu_junction &x, const ygpu_junction &y) { return x.read < y.read; });
+    devReads += b.devStats[0]; devSkipped += b.devStats[2]; devHandedBack += b.devStats[3];
+    hostReads += b.hostReads; hostSkipped += b.hostSkipped;
 }
 
 bool JunctionTrack::deviceEntryPoints() { return ygpu_junctions_enable != nullptr && ygpu_junctions_size != nullptr && ygpu_junctions_collect != nullptr; }
 
-int JunctionTrack::deviceEnable(ygpu_ctx *ctx) const
+int JunctionTrack::enable(const CtxAt &at)
 {
-    if (!deviceEntryPoints()) return YGPU_ENODEV;
-    ygpu_junction_params p; p.min_mapq = minMapq; p.n_seqs = (uint32_t)seqStart.size(); p.seq_start = seqStart.data(); p.seq_length = seqLength.data();
-    return ygpu_junctions_enable(ctx, &p);
+    if (!deviceEntryPoints() || getenv("YAHA_HOST_JUNCTIONS") != nullptr) return YGPU_ENODEV;
+    ygpu_junction_params p; p.min_mapq = minMapq; seqs.into(p);
+    const int rc = ygpu_junctions_enable(at.ctx, &p); return rc == YGPU_ENOMEM ? YGPU_ENODEV : rc;
 }
 
-int JunctionTrack::deviceCollect(ygpu_ctx *ctx, std::vector<ygpu_junction> &out, uint64_t stats[4]) const
+int JunctionTrack::afterFilter(const CtxAt &at, Slot *s)
 {
-    out.clear();
-    if (!deviceEntryPoints()) return YGPU_ENODEV;
-    uint64_t n = 0; int rc = ygpu_junctions_size(ctx, &n); if (rc != 0) return rc;
-    out.resize((size_t)n);
-    return ygpu_junctions_collect(ctx, out.data(), stats);
+    Batch &b = *static_cast<Batch *>(s); b.dev.clear();
+    uint64_t n = 0; int rc = ygpu_junctions_size(at.ctx, &n); if (rc != 0) return rc;
+    b.dev.resize((size_t)n);
+    return ygpu_junctions_collect(at.ctx, b.dev.data(), b.devStats);
+}
+
+// the run's junctions clustered and written
+bool JunctionTrack::finish(FILE *mainOut, FILE *log, bool)
+{
+    std::string jerr; nJunctions = all.size();
+    if (fflush(mainOut) != 0) return false;
+    if (!write(file.c_str(), *genome, jerr)) { fprintf(log, "%s\n", jerr.c_str()); return false; }
+    return true;
+}
+
+void JunctionTrack::stats(std::string &line) const
+{
+    char t[256]; snprintf(t, sizeof t, ", \"bp_device_reads\": %llu, \"bp_host_reads\": %llu, \"bp_junctions\": %llu, \"bp_clusters\": %llu", (unsigned long long)devReads,
+        (unsigned long long)hostReads, (unsigned long long)nJunctions, (unsigned long long)nClusters);
+    line += t;
 }
 
 // Clusters: the junctions sorted by (seqA, strandA, seqB, strandB, posA, posB, qgap); in that order a junction joins the FIRST cluster, in creation order, of its

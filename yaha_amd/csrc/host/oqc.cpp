@@ -104,4 +104,13 @@ void oqcParamsFromArgs(const Args &a, yoqc::Params &P, std::vector<uint32_t> &th
         P.FBS = a.FBS ? 1 : 0;
     P.FBS_PSLength = a.FBS_PSLength; P.FBS_PSScore = a.FBS_PSScore; P.bppVmin = t.vmin; P.bppN = useTable ? (int)thr.size() : -1; P.bppThr = thr.data();
 }
+
+bool postfilterParams(const Args &a, const SeqTable &seqs, std::vector<uint32_t> &thr, ygpu_postfilter_params *p)
+{
+    yoqc::Params P; oqcParamsFromArgs(a, P, thr);
+    memset(p, 0, sizeof *p);
+    p->minNonOverlap = P.minNonOverlap; p->BPCost = P.BPCost; p->maxBPLog = P.maxBPLog; p->FBS = P.FBS; p->FBS_PSLength = P.FBS_PSLength; p->FBS_PSScore = P.FBS_PSScore;
+    p->bppVmin = P.bppVmin; p->bppN = std::max(0, P.bppN); p->bppThr = thr.data(); seqs.into(*p);
+    return a.OQC && P.bppN >= 0 && P.minNonOverlap >= 1;
+}
 }  // namespace yaha

@@ -27,11 +27,16 @@ __attribute__((weak)) int ygpu_pileup_gather(ygpu_ctx *ctx, const uint32_t *slot
 
 namespace yaha {
 
-PileupTrack::PileupTrack(int minAltReads)
-    : BinnedTrack({"-opu", "-opu", "pileup", "pileup"}, (uint32_t)ypileup::NCH,
+PileupTrack::PileupTrack()
+    : BinnedTrack({"-opu", "-opu", "pileup", "pileup", "YAHA_HOST_PILEUP",
+                   ", \"pileup_bases\": %llu, \"pileup_device_records\": %llu, \"pileup_host_records\": %llu, \"pileup_counted\": %llu"}, (uint32_t)ypileup::NCH,
                   ygpu_pileup_enable != nullptr && ygpu_pileup_candidates_size != nullptr && ygpu_pileup_candidates_collect != nullptr && ygpu_pileup_gather != nullptr,
-                  ygpu_pileup_size, ygpu_pileup_collect),
-      minAlt((uint32_t)minAltReads) {}
+                  ygpu_pileup_size, ygpu_pileup_collect) {}
+
+bool PileupTrack::setup(const Args &a, const Genome &g, int nImages, int nContexts, std::string &err)
+{
+    minAlt = (uint32_t)a.puMinAlt; return init(g, a.puFileName, 1, a.puMinQ, nImages, nContexts, err);
+}
 
 PileupTrack::~PileupTrack() { for (uint32_t *b : blocks) free(b); }
 
@@ -55,7 +60,7 @@ uint32_t *PileupTrack::block(uint32_t slot)
     free(fresh); return b;
 }
 
-void PileupTrack::add(const OutClump &oc, const Read &r)
+void PileupTrack::add(const OutClump &oc, const Read &r, Slot *)
 {
     const uint64_t n = nBins; uint64_t added = 0;
     countRecord(ypileup::walkClump(layout(), oc.c, oc.ops, r.fwdCodes.data(), (uint32_t)r.fwdCodes.size(), (oc.status & 0x01) != 0, oc.mapQuality,
@@ -69,7 +74,7 @@ void PileupTrack::add(const OutClump &oc, const Read &r)
 int PileupTrack::deviceEnable(ygpu_ctx *ctx) const
 {
     if (!deviceEntryPoints()) return YGPU_ENODEV;
-    ygpu_pileup_params p; p.min_mapq = minMapq; p.n_seqs = (uint32_t)seqStart.size(); p.seq_start = seqStart.data(); p.seq_length = seqLength.data();
+    ygpu_pileup_params p; p.min_mapq = minMapq; seqs.into(p);
     return ygpu_pileup_enable(ctx, &p);
 }
 

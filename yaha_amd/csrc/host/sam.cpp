@@ -96,4 +96,30 @@ void printClump(const Args &a, const Genome &g, const Read &r, const OutClump &o
         out.len += (size_t)(w - w0);
     }
 }
+
+// ---- the main output as text: the header, then every batch's text as the formatter wrote it -------------------------------------------------------------------
+bool RecordSink::open(const std::string &file, FILE *log)
+{
+    path = file; out = file == "stdout" ? stdout : fopen(file.c_str(), "w");
+    if (!out) { fprintf(log, "Failure to open output file: %s.\n", file.c_str()); return false; }
+    setvbuf(out, nullptr, _IONBF, 0); return true;
+}
+bool RecordSink::begin(const Args &, const Genome &, const std::string &samHeader, int, FILE *log)
+{
+    if (fputs(samHeader.c_str(), out) < 0) { fprintf(log, "Failure writing the output file.\n"); return false; }
+    return true;
+}
+bool RecordSink::writeBytes(const Text &t, std::string &err)
+{
+    if (t.len && fwrite(t.p, 1, t.len, out) != t.len) { err = "Failure writing the output file"; return false; }
+    return true;
+}
+bool RecordSink::write(SinkBatch &b, std::string &err) { return writeBytes(b.text, err); }
+bool RecordSink::close(bool stopped, FILE *log)
+{
+    bool ok = true;
+    if (out && (fflush(out) != 0 || ferror(out))) { if (!stopped) fprintf(log, "Failure writing the output file.\n"); ok = false; }
+    if (out && out != stdout && fclose(out) != 0) { fprintf(log, "Failure closing the output file.\n"); ok = false; }
+    out = nullptr; return ok;
+}
 }  // namespace yaha

@@ -193,30 +193,74 @@ struct BamSorter {
 void bamSortOrder(const BamEntry *entries, size_t n, uint32_t *perm);      // the host's ordering (stable): perm[j] = the record at sorted place j
 std::string baiBuild(const BamEntry *sorted, size_t n, size_t nRefs, const uint64_t *coffs, size_t nBlocks);
 
+// ---- the genome's sequence table, as every device stage's parameter block takes it ---------------------------------------------------------------------------
+struct SeqTable {
+    std::vector<uint32_t> start, length;
+    void set(const Genome &g) { start.clear(); length.clear(); for (auto &sq : g.seqs) { start.push_back(sq.start); length.push_back(sq.length); } }
+    template <class P> void into(P &p) const { p.n_seqs = (uint32_t)start.size(); p.seq_start = start.data(); p.seq_length = length.data(); }
+};
+
+// ---- a side output of a query run: a file beside the alignments, made of the records that are printed (the kinds follow) -------------------------------------
+// The run driver (pipeline.cpp) knows the outputs by this interface alone, as a list: output k is bit k of a batch's onDevice mask -- the device stage behind
+// the post-filter did the batch's share of it, all but the reads it handed back unfiltered -- and owns slot k of every batch object.  Every hook defaults to
+// "nothing to do".  The device entry points of a kind are weak references: host code links and runs without them (the CPU tier's test doubles).
+struct CtxAt { ygpu_ctx *ctx; int index, image, device; };                // a context of the run: its number, the index image it shares, the HIP device
+struct SideOutput {
+    struct Slot { virtual ~Slot() {} };                                   // what a kind keeps with a batch; made once per batch object, reused with it
+    virtual ~SideOutput() {}
+    virtual const char *name() const = 0;                                 // the option of its file: how messages speak of it
+    // set-up: the kind's own options; nImages index images (-gpus), nContexts contexts in all
+    virtual bool setup(const Args &a, const Genome &g, int nImages, int nContexts, std::string &err) = 0;
+    // per context, by its thread, before its first batch: 0 = the device does this context's batches; YGPU_ENOMEM = no room on the device, the run stops with
+    // ygpu_last_error; anything else (no entry points in this build, the kind's YAHA_HOST_* switch, a refusal) = the formatters do them
+    virtual int  enable(const CtxAt &) { return YGPU_ENODEV; }
+    // per batch of such a context, by the thread that runs its post-filter: before ygpu_postfilter (list order) and after it (reverse order)
+    virtual int  beforeFilter(const CtxAt &, size_t /*batchBases*/) { return 0; }
+    virtual int  afterFilter(const CtxAt &, Slot *) { return 0; }
+    // per batch by the formatter thread that has it: beginBatch (onDevice: the slot holds what afterFilter put there), then add for every printed record and
+    // endRead (wantsReads) for every read with its printed records -- those the device did not do --, then endBatch
+    virtual Slot *newSlot() const { return nullptr; }
+    virtual void beginBatch(Slot *, bool /*onDevice*/) const {}
+    virtual void add(const OutClump &, const Read &, Slot *) {}
+    virtual bool wantsReads() const { return false; }
+    virtual void endRead(const OutClump *, uint32_t /*n*/, const Read &, uint32_t /*read*/, Slot *) const {}
+    virtual void endBatch(Slot *) {}
+    virtual void written(Slot *) {}                                       // per batch by the writer thread, in ticket order
+    // the end of a run that got there: what the devices hold joins the host's, mainOut is flushed, the file is written; false: failed, with a line in log
+    virtual bool finish(FILE *mainOut, FILE *log, bool timing) = 0;
+    virtual void stats(std::string &line) const = 0;                      // its keys of the stats line, each with its leading ", "
+};
+
 // ---- the binned tracks: read depth (-ocov), the evidence track (-oev) and the allele pileup (-opu) (depth.cpp, events.cpp, pileup.cpp; ../*_core.h) --------
 // The host's array of a track, in the layout the device uses (one routine a kind, *_core.h): `channels` uint32 a bin, bin-major.  The formatter threads add the
 // records the device did NOT count -- runs whose post-filter stays on the host (-dpf N, -OQC N, YAHA_HOST_OQC=1), the reads the device stage hands back
-// unfiltered, and everything when the library has no device entry points for the track or refuses to enable them -- with relaxed atomics.  At the end of the
-// run the device's arrays (one per index image) are added and the file is written after the last alignment.  A kind adds what differs: what a record adds, the
-// parameters of its device stage, its entry points -- looked up weakly: host code links and runs without them (the CPU tier's test doubles) -- and its lines.
-struct BinnedTrack {
-    // the words a kind is spoken of with: the options of the bin size and of the file, the array's noun, the file's
-    struct Names { const char *binOpt, *fileOpt, *array, *file; };
+// unfiltered, and everything when the library has no device entry points for the track or refuses to enable them -- with relaxed atomics.  The device stage
+// feeds an array of its own per index image, enabled by every context of the image (the first makes it): at the end of the run the arrays are added -- each
+// through its feeder, the first context of the image to post-filter a batch (such a context is never left out afterwards) -- and the file is written after the
+// last alignment.  A kind adds what differs: its options, what a record adds, the parameters of its device stage, its entry points and its lines.
+struct BinnedTrack : SideOutput {
+    // the words a kind is spoken of with: the options of the bin size and of the file, the array's noun, the file's, the switch that keeps it on the host, its keys
+    // of the stats line (bins, device records, host records, sum)
+    struct Names { const char *binOpt, *fileOpt, *array, *file, *hostSwitch, *statsFmt; };
     typedef int (*SizeFn)(ygpu_ctx *, uint64_t *);
     typedef int (*CollectFn)(ygpu_ctx *, uint32_t *, uint64_t[4]);
     // what the kind is: how it is spoken of, its words a bin, its device entry points (null in a build without them)
     const Names names; const uint32_t channels;
   private:
     const bool haveEnable; const SizeFn devSize; const CollectFn devCollect;
+    const Genome *genome = nullptr; std::string file; std::vector<CtxAt> ctxs; std::vector<std::atomic<int>> feeder;      // feeder[k]: 1 + the context that feeds image k
   public:
-    std::vector<uint32_t> seqStart, seqLength, binBase; uint64_t nBins = 0; uint32_t bin = 100, minMapq = 0;
+    SeqTable seqs; std::vector<uint32_t> binBase; uint64_t nBins = 0; uint32_t bin = 100, minMapq = 0;
     uint32_t *data = nullptr;                                             // nBins * channels words, zeroed; relaxed atomic adds
     uint64_t hostRecords = 0, hostSkipped = 0, hostDropped = 0;           // (atomic adds as well) records the host counted / gated by MAPQ / dropped
     uint64_t devRecords = 0, devSkipped = 0, devDropped = 0, devHandedBack = 0;
     BinnedTrack(const BinnedTrack &) = delete; BinnedTrack &operator=(const BinnedTrack &) = delete;
-    virtual ~BinnedTrack() { free(data); }
-    bool init(const Genome &g, int binBases, int minQ, std::string &err);    // the layout, then the kind's host storage (allocate)
-    virtual void add(const OutClump &oc, const Read &r) = 0;              // one record printClump was called for, and its read (its length; the pileup: its bases)
+    ~BinnedTrack() override { free(data); }
+    const char *name() const override { return names.fileOpt; }
+    int  enable(const CtxAt &at) override;
+    int  beforeFilter(const CtxAt &at, size_t) override;                  // (the image's feeder)
+    bool finish(FILE *mainOut, FILE *log, bool timing) override;
+    void stats(std::string &line) const override;
     bool deviceEntryPoints() const { return haveEnable && devSize && devCollect; }      // does this build have the kind's ygpu_*_enable / _size / _collect?
     virtual int deviceEnable(ygpu_ctx *ctx) const = 0;                    // YGPU_ENODEV without the entry points
     int  deviceCollect(ygpu_ctx *ctx, std::string &err);                  // adds the image's array and statistics to this track
@@ -230,22 +274,26 @@ struct BinnedTrack {
     bool write(const char *path, const Genome &g, std::string &err) const;      // path "stdout" = standard output
   protected:
     BinnedTrack(const Names &nm, uint32_t ch, bool enable, SizeFn sz, CollectFn co) : names(nm), channels(ch), haveEnable(enable), devSize(sz), devCollect(co) {}
-    ydepth::Layout layout() const { return ydepth::Layout{seqStart.data(), seqLength.data(), binBase.data(), (uint32_t)seqStart.size(), bin, minMapq}; }
+    // (a kind's setup: its file, the layout, then its host storage -- allocate)
+    bool init(const Genome &g, const std::string &path, int binBases, int minQ, int nImages, int nContexts, std::string &err);
+    ydepth::Layout layout() const { return ydepth::Layout{seqs.start.data(), seqs.length.data(), binBase.data(), (uint32_t)seqs.start.size(), bin, minMapq}; }
     void countRecord(int gate);                                           // what became of a record the host walked (ydepth::COUNTED ...)
     virtual bool allocate(std::string &err);                              // the host's storage for nBins bins: here the dense, zeroed `data`
     virtual bool writeLines(FILE *f, const Genome &g) const = 0;          // the kind's lines; false: a write failed
 };
-struct DepthTrack : BinnedTrack {                                         // bedGraph of the covered bases
+struct DepthTrack : BinnedTrack {                                         // bedGraph of the covered bases (-covbin, -covq)
     DepthTrack();
-    void add(const OutClump &oc, const Read &r) override;
+    bool setup(const Args &a, const Genome &g, int nImages, int nContexts, std::string &err) override;
+    void add(const OutClump &oc, const Read &r, Slot *) override;
     int  deviceEnable(ygpu_ctx *ctx) const override;
   protected:
     bool writeLines(FILE *f, const Genome &g) const override;
 };
-struct EventsTrack : BinnedTrack {                                        // mismatched bases, deleted bases, insertions, clipped ends left and right
+struct EventsTrack : BinnedTrack {                                        // mismatched bases, deleted bases, insertions, clipped ends left and right (-evbin, -evq, -evclip)
     uint32_t minClip = 1;
-    explicit EventsTrack(int minClipBases);
-    void add(const OutClump &oc, const Read &r) override;
+    EventsTrack();
+    bool setup(const Args &a, const Genome &g, int nImages, int nContexts, std::string &err) override;
+    void add(const OutClump &oc, const Read &r, Slot *) override;
     int  deviceEnable(ygpu_ctx *ctx) const override;
   protected:
     bool writeLines(FILE *f, const Genome &g) const override;
@@ -255,16 +303,17 @@ struct EventsTrack : BinnedTrack {                                        // mis
 // lists its candidates (nonref >= 1), every image gathers its counts at the sorted union, the host adds its own and applies minAlt (mergeDevices).  Nothing
 // dense on the host either: its counts live in blocks of kBlock slots, made when a formatter thread first adds to one (`data` stays null) -- a pointer per
 // block, 6 MB of them at 3.1 Gbp, and 112 KB for every block the host's share of the records touches.
-struct PileupTrack : BinnedTrack {
+struct PileupTrack : BinnedTrack {                                        // (a bin of one base, seven channels; -pumin, -puq)
     enum : uint32_t { kBlock = 4096 };
     uint32_t minAlt = 2;
     std::vector<uint32_t *> blocks;                                       // blocks[slot / kBlock]: kBlock * 7 zeroed words, or null (atomic loads, made by compare-and-swap)
     uint64_t hostCounted = 0, devCounted = 0, nCandidates = 0;            // counts added by the formatters / on the devices; slots of the union
     struct Site { uint32_t slot, ref; uint32_t n[7]; };                   // ref: the reference's 4-bit code
     std::vector<Site> sites;                                              // what writeLines prints, ascending (made by mergeDevices)
-    explicit PileupTrack(int minAltReads);
+    PileupTrack();
     ~PileupTrack() override;
-    void add(const OutClump &oc, const Read &r) override;
+    bool setup(const Args &a, const Genome &g, int nImages, int nContexts, std::string &err) override;
+    void add(const OutClump &oc, const Read &r, Slot *) override;
     int  deviceEnable(ygpu_ctx *ctx) const override;
     int  mergeDevices(ygpu_ctx *const *feeders, int n, const Genome &g, int *failed, std::string &err) override;
     uint64_t sum() const override { return hostCounted + devCounted; }    // (the counts added: the sum over the arrays without reading 28 bytes a base)
@@ -281,52 +330,114 @@ struct PileupTrack : BinnedTrack {
 
 // ---- split-read breakpoint calls (-obp; junctions.cpp, ../junction_core.h) ---------------------------------------------------------------------------------
 // The junctions of the whole run, their clustering and the BEDPE writer.  The junctions of a batch are made on the device behind its post-filter
-// (ygpu_junctions_*, looked up weakly as the tracks' entry points are) and travel with the batch; the formatter threads make the ones the device did not -- the
-// reads it handed back unfiltered, runs whose post-filter stays on the host, builds without the entry points -- with the same routine (junction_core.h).  The
-// writer thread adds every batch's junctions in ticket order, merged by read: the list is in read order whatever -ctx and -batch are.
-struct JunctionTrack {
-    std::vector<uint32_t> seqStart, seqLength; uint32_t minMapq = 0, window = 10;
+// (ygpu_junctions_*), per context and per batch, nothing shared, and travel with the batch in its slot; the formatter threads make the ones the device did not
+// -- the reads it handed back unfiltered, runs whose post-filter stays on the host, builds without the entry points, YAHA_HOST_JUNCTIONS -- with the same
+// routine (junction_core.h), from a read's printed records.  The writer thread adds every batch's junctions in ticket order, merged by read: the list is in
+// read order whatever -ctx and -batch are.
+struct JunctionTrack : SideOutput {
+    SeqTable seqs; uint32_t minMapq = 0, window = 10;
     std::vector<ygpu_junction> all;                                       // (read: the index within its batch; not used after the merge)
-    uint64_t devReads = 0, hostReads = 0, devSkipped = 0, hostSkipped = 0, devHandedBack = 0, nClusters = 0;      // reads with junctions by who made them ...
-    void init(const Genome &g, int minQ, int w);
-    // the junctions of one read's printed records on the host, appended to out (ordinal order); returns their number; *skipped: records gated by MAPQ alone
-    uint32_t addRead(const OutClump *recs, uint32_t n, int qlen, uint32_t read, std::vector<ygpu_junction> &out, uint32_t *skipped) const;
-    // one batch, in output order: the device's junctions (read order) and the formatter's (read order) merged by read; hostReadsB / hostSkippedB: the formatter's counts
-    void addBatch(const ygpu_junction *dev, size_t nDev, const uint64_t devStats[4], const std::vector<ygpu_junction> &host, uint64_t hostReadsB, uint64_t hostSkippedB);
+    uint64_t devReads = 0, hostReads = 0, devSkipped = 0, hostSkipped = 0, devHandedBack = 0, nClusters = 0, nJunctions = 0;      // reads with junctions by who made them ...
+    // a batch's: the junctions the device made and its statistics; the ones the formatter made, and its counts
+    struct Batch : Slot { std::vector<ygpu_junction> dev, host; uint64_t devStats[4] = {0, 0, 0, 0}, hostReads = 0, hostSkipped = 0; };
+    const char *name() const override { return "-obp"; }
+    bool setup(const Args &a, const Genome &g, int nImages, int nContexts, std::string &err) override;      // -bpq, -bpw
+    int  enable(const CtxAt &at) override;                                // (no room for a context's lists: the formatters make its junctions)
+    int  afterFilter(const CtxAt &at, Slot *s) override;                  // the junctions of the context's last ygpu_postfilter: few, and on their way while the clumps are sized
+    Slot *newSlot() const override { return new Batch; }
+    void beginBatch(Slot *s, bool onDevice) const override;
+    bool wantsReads() const override { return true; }
+    // the junctions of one read's printed records on the host, appended to the batch's (ordinal order)
+    void endRead(const OutClump *recs, uint32_t n, const Read &r, uint32_t read, Slot *s) const override;
+    // one batch, in output order: the device's junctions (read order) and the formatter's (read order) merged by read
+    void written(Slot *s) override;
+    bool finish(FILE *mainOut, FILE *log, bool timing) override;
+    void stats(std::string &line) const override;
     static bool deviceEntryPoints();                                      // does this build have ygpu_junctions_*?
-    int  deviceEnable(ygpu_ctx *ctx) const;                               // YGPU_ENODEV without the entry points
-    int  deviceCollect(ygpu_ctx *ctx, std::vector<ygpu_junction> &out, uint64_t stats[4]) const;      // the junctions of the context's last ygpu_postfilter
     bool write(const char *path, const Genome &g, std::string &err);      // clusters and writes; path "stdout" = standard output
+  private:
+    const Genome *genome = nullptr; std::string file;
 };
 
 // ---- indel alleles (-oid; indels.cpp, ../indel_core.h) --------------------------------------------------------------------------------------------------------
 // The run's alleles -- (slot, type, length, inserted bases) -> records that carry it -- and their writer.  The device counts them in a hash table per context
-// behind its post-filter (ygpu_indels_*, looked up weakly as the tracks' entry points are): the pipeline drains a context's table whenever more than a quarter
-// of it is in use, and once more at the end.  The formatter threads count what the device did not -- runs whose post-filter stays on the host, the reads it
-// hands back unfiltered, builds without the entry points -- with the same walk (indel_core.h) into a list of their own per batch, merged here under a lock.
+// behind its post-filter (ygpu_indels_*): a context's table is drained BEFORE a batch that could take it past one half (a batch has at most one event per two
+// bases), whenever more than a quarter of it is in use after one, and once more at the end.  The table has two entries per base of the largest batch the
+// splitter cuts (indel_core.h tableCapacity), as far as that is known before the reads are: -batch N gives a read count, and N reads of the greatest length
+// would ask for more than a batch ever holds -- the table then stops at that of the default batch, and the drain before a batch keeps the load where the rule
+// wants it.  The formatter threads count what the device did not -- runs whose post-filter stays on the host, the reads it hands back unfiltered, builds
+// without the entry points, YAHA_HOST_INDELS -- with the same walk (indel_core.h) into the batch's slot, merged here under a lock once per batch.
 struct IndelKey { uint64_t w0, w1, w2; };
 struct IndelKeyLess { bool operator()(const IndelKey &a, const IndelKey &b) const; };      // the order of the file (indel_core.h keyLess)
-struct IndelTrack {
-    std::vector<uint32_t> seqStart, seqLength, binBase; uint64_t nSlots = 0; uint32_t minMapq = 0, minLen = 1, minCount = 2;
+struct IndelTrack : SideOutput {
+    SeqTable seqs; std::vector<uint32_t> binBase; uint64_t nSlots = 0, capacity = 0; uint32_t minMapq = 0, minLen = 1, minCount = 2;
     std::mutex mu; std::map<IndelKey, uint64_t, IndelKeyLess> alleles;
     uint64_t hostRecords = 0, hostSkipped = 0, hostDropped = 0, hostEvents = 0;           // (under mu, by merge)
     uint64_t devRecords = 0, devSkipped = 0, devDropped = 0, devEvents = 0, devHandedBack = 0, devLost = 0, drains = 0, nLines = 0;
     // what a formatter thread gathers of one batch before it merges: the events' keys and what became of the records it walked
-    struct Local { std::vector<IndelKey> keys; uint64_t records = 0, skipped = 0, dropped = 0; };
-    bool init(const Genome &g, int minQ, int minLength, int minRecords, std::string &err);
-    void add(const OutClump &oc, const Read &r, Local &local) const;      // one record printClump was called for
-    void merge(Local &local);                                             // ... and the batch's share into the run's alleles; clears local
+    struct Local : Slot { std::vector<IndelKey> keys; uint64_t records = 0, skipped = 0, dropped = 0; };
+    const char *name() const override { return "-oid"; }
+    bool setup(const Args &a, const Genome &g, int nImages, int nContexts, std::string &err) override;      // -idq, -idlen, -idmin; the table's capacity
+    int  enable(const CtxAt &at) override;                                // (remembers the context for the end of the run)
+    int  beforeFilter(const CtxAt &at, size_t batchBases) override;
+    int  afterFilter(const CtxAt &at, Slot *) override;
+    Slot *newSlot() const override { return new Local; }
+    void add(const OutClump &oc, const Read &r, Slot *s) override;        // one record printClump was called for
+    void endBatch(Slot *s) override;                                      // ... and the batch's share into the run's alleles; clears the slot
+    bool finish(FILE *mainOut, FILE *log, bool timing) override;          // what every context's table still holds, then the file
+    void stats(std::string &line) const override;
     static bool deviceEntryPoints();                                      // does this build have ygpu_indels_*?
-    int  deviceEnable(ygpu_ctx *ctx, uint64_t capacity) const;            // YGPU_ENODEV without the entry points
-    int  deviceSize(ygpu_ctx *ctx, uint64_t *used) const;
     int  deviceDrain(ygpu_ctx *ctx, bool duringRun, std::string &err);    // collects and clears the context's table into the run's alleles
     bool write(const char *path, const Genome &g, std::string &err);      // applies minCount; path "stdout" = standard output
+  private:
+    int drainAbove(ygpu_ctx *ctx, uint64_t more, uint64_t limit);         // drains the table if it holds entries and they, with `more`, pass limit
+    const Genome *genome = nullptr; std::string file; std::vector<CtxAt> enabled;
 };
+
+// ---- the main output of a query run: where the formatted records of the batches go (sam.cpp: SAM / Blast8 text; bam.cpp: BAM, sorted BAM) -----------------
+// What of a batch belongs to the main output: the device it ran on, its records as the formatter wrote them, as BGZF blocks (-obh / -obs) with the time their
+// compression took, one entry per record in the order of the text (-obsort), the records written into the text
+struct SinkBatch { int dev = 0; Text text, packed; double tPack = 0; std::vector<BamEntry> entries; uint64_t records = 0; };
+// This one writes text: the header at the start, every batch's text with one call.  bam.cpp has the two others.
+struct RecordSink {
+    FILE *out = nullptr; std::string path;
+    virtual ~RecordSink() {}
+    bool open(const std::string &file, FILE *log);                        // "stdout" = standard output; unbuffered: whole batches are written with one call each
+    virtual bool begin(const Args &a, const Genome &g, const std::string &samHeader, int nFormatters, FILE *log);      // the header; false: failed, with a line in log
+    virtual std::vector<BamEntry> *entries(SinkBatch &) const { return nullptr; }      // where the formatter lists the batch's records, if the sink wants that
+    virtual bool pack(SinkBatch &, int /*formatter*/, bool /*stopped*/, std::string &) { return true; }      // per batch by formatter thread 0 .. nFormatters - 1
+    virtual bool write(SinkBatch &b, std::string &err);                   // per batch by the writer thread, in ticket order
+    virtual void timingLine(const SinkBatch &, uint64_t /*ticket*/) const {}      // the sink's own YAHA_TIMING line of a batch written
+    virtual bool finish(FILE *) { return true; }                          // after the last batch of a run that got there
+    virtual void abandon() {}                                             // a run that failed: a sink that writes nothing before the end leaves no file behind
+    bool close(bool stopped, FILE *log);                                  // flushes and closes; false: failed, with a line in log unless the run had stopped
+    virtual void stats(std::string &) const {}                            // its keys of the stats line, each with its leading ", "
+  protected:
+    bool writeBytes(const Text &t, std::string &err);
+};
+std::unique_ptr<RecordSink> makeRecordSink(const Args &a);                // by -obh / -obs / -obsort
+
+// ---- what the formatting of a batch works with (pipeline.cpp): filled by a formatter thread of the command line and by yaha_session_emit[_filtered] ---------
+struct FormatCtx {
+    const Args &args; const Genome &genome; const Read *reads;            // the batch's reads
+    const std::vector<std::unique_ptr<SideOutput>> *outputs = nullptr; SideOutput::Slot *const *slots = nullptr; unsigned wantReads = 0;      // (mask: outputs with endRead)
+    std::vector<BamEntry> *bamEntries = nullptr; uint64_t bamRecords = 0; // -obsort: the batch's list; -obh / -obs: records written into the text
+};
+// OQC/FBS filter + output text of one batch.  nt > 1: the reads of the batch are cut into nt contiguous ranges, one thread each (the ctypes/Session path, one
+// batch at a time); the command line formats whole batches on a pool of threads instead and passes nt = 1.
+void formatBatch(FormatCtx &f, const ygpu_result_batch *r, Text &text, int nt);
+// ... of a batch whose post-filter ran on the device (ygpu_postfilter): the clumps arrive in print order with the filter's fields set.  onDevice: the side
+// outputs the device stage did for the batch -- all but the reads it handed back unfiltered
+void formatFiltered(FormatCtx &f, const ygpu_filtered_batch *r, Text &text, unsigned onDevice = 0);
 }  // namespace yaha
 namespace yoqc { struct Params; }
 namespace yaha {
 // the post-filter's parameters in the form oqc_core.h takes them (host and device stage); thr receives the break point table P points into
 void oqcParamsFromArgs(const Args &a, yoqc::Params &P, std::vector<uint32_t> &thr);
+// ... and in the form ygpu_set_postfilter takes them (p points into thr and seqs).  false: the run is not one the device stage takes -- OQC runs with break
+// point costs that are a step function and -MNO of at least 1 only.  (-MNO below 1: the graph's successor test then also lets a node relax itself and nodes
+// before it, which the device stage's one-successor-per-lane step does not order the way the sequential loop does, GraphPath.cpp:633-700)
+bool postfilterParams(const Args &a, const SeqTable &seqs, std::vector<uint32_t> &thr, ygpu_postfilter_params *p);
 
 // ---- whole-run driver (replacement of processQueryFile, Query.c:551-709) --------------------------------
 int effectiveCpus();                                    // affinity mask and control-group CPU quota
@@ -335,3 +446,13 @@ int runIndex(Args &a, FILE *log);
 int runCompress(Args &a, FILE *log);                     // -c: compressFile only (Main.c:572-577)
 int runUncompress(Args &a, FILE *log);                   // -u: uncompressFile, Compress.c:337-397 (50 bases a line)
 }  // namespace yaha
+
+// ---- the session behind the C-ABI's yaha_session_* (session.cpp); a command-line run loads one as well ------------------------------------------------------
+struct yaha_session {
+    yaha::Args args; yaha::Genome genome; yaha::IndexFile index; yaha::ReadReader reader; std::string err, header; yaha::Text text;
+    yaha::SeqTable seqs;                                                  // the genome's sequence table (load): what every yaha_session_*_params points into
+    std::vector<uint32_t> pfThr;                                          // the break point table yaha_session_postfilter_params points into
+    std::vector<yaha::Read> reads; std::vector<uint8_t> codes; std::vector<uint64_t> offsets;
+    bool readerOpen = false;
+    bool load();                                                          // genome, index, input, header; false with err
+};
