@@ -330,6 +330,33 @@ int  ygpu_indels_enable(ygpu_ctx *ctx, const ygpu_indel_params *p);            /
 int  ygpu_indels_size(ygpu_ctx *ctx, uint64_t *used);
 int  ygpu_indels_collect(ygpu_ctx *ctx, ygpu_indel_entry *out, uint64_t stats[6]);
 
+/* ---- the error profile: how good the printed alignments are (optional, behind ygpu_postfilter) -----------------------------------------------------------------
+ * What the other outputs leave out: the substitution spectrum, the lengths of insertions and deletions, the identity the records reach and the error rate
+ * along the read.  With ygpu_eprofile_enable, every ygpu_postfilter of the context also adds the clumps it returns to ONE table of YGPU_EPROFILE_WORDS = 1556
+ * uint64 words on the device.  The contract (yaha_amd/csrc/eprofile_core.h -- one set of routines for host and device): gates, the two-sequence drop and the
+ * walk are the pileup's; a PAIR is a reference base under an M or R op with the read base over it, both as channels A C G T N (the reference's from the packed
+ * image, past the image N), a MATCH a pair of equal channels that are not N.  The words, in this order:
+ *   SUB    25         [ref channel][read channel], 1 per pair
+ *   INS    65         1 per I op of n >= 1 bases at index min(n, 65) - 1
+ *   DEL    65         the same per D op
+ *   IDENT  1001       1 per record with cols > 0 at floor(1000 * matches / cols), cols = pairs + inserted + deleted bases
+ *   POS    100 x 4    by the pair's place in the read as sequenced, bin = forward offset * 100 / read length: pairs, pairs that are no match, I ops, D ops
+ * The reads the stage hands back unfiltered (primaryCount 0xFFFF) are NOT counted: the caller filters them and counts what it prints.  While the stage is
+ * enabled ygpu_postfilter_snapshot also copies the batch's forward codes and read offsets (as for the pileup).
+ * The table is the CONTEXT's own (a caller with several contexts adds their tables up): the kernel keeps it in LDS for a workgroup's whole share of a batch
+ * and reaches memory once per workgroup.  ygpu_eprofile_size: the number of words, YGPU_EPROFILE_WORDS.  ygpu_eprofile_collect: the table as it stands --
+ * nothing is cleared -- after waiting for the filter stages queued on the context so far; words and stats may each be NULL.  stats: records counted, records
+ * skipped (MAPQ), records dropped (two sequences), reads left to the caller.  A parked context (ygpu_park) has given its table up: all zero.
+ * Order: ygpu_set_postfilter, ygpu_eprofile_enable, then batches (ygpu_run, ygpu_postfilter ...), then ygpu_eprofile_collect. */
+#define YGPU_EPROFILE_WORDS 1556
+typedef struct ygpu_eprofile_params {
+    uint32_t min_mapq, n_seqs;
+    const uint32_t *seq_start, *seq_length;            /* reference sequences in bases, ascending (host memory; copied) */
+} ygpu_eprofile_params;
+int  ygpu_eprofile_enable(ygpu_ctx *ctx, const ygpu_eprofile_params *p);        /* after ygpu_set_postfilter */
+int  ygpu_eprofile_size(ygpu_ctx *ctx, uint64_t *n_words);
+int  ygpu_eprofile_collect(ygpu_ctx *ctx, uint64_t *words, uint64_t stats[4]);
+
 /* ---- split-read breakpoint calls: where the printed alignments of a read join (optional, behind ygpu_postfilter) ----------------------------------------------
  * The primary signal of a structural-variant caller.  With ygpu_junctions_enable, every ygpu_postfilter of the context also makes the JUNCTIONS of its batch on
  * the device.  The contract (yaha_amd/csrc/junction_core.h -- one set of routines for host and device): the eligible records of a read are the printed ones (a
@@ -473,6 +500,8 @@ int  yaha_session_events_params(yaha_session *s, ygpu_events_params *p);
 int  yaha_session_pileup_params(yaha_session *s, ygpu_pileup_params *p);
 /* The same for ygpu_indels_enable: -idq (default 0), -idlen (default 1), capacity 0 and the sequence table (pointers of their own into the session). */
 int  yaha_session_indel_params(yaha_session *s, ygpu_indel_params *p);
+/* The same for ygpu_eprofile_enable: -epq (default 0) and the sequence table (pointers of their own into the session). */
+int  yaha_session_eprofile_params(yaha_session *s, ygpu_eprofile_params *p);
 /* The same for ygpu_junctions_enable: -bpq (default 0) and the sequence table (pointers of their own into the session). */
 int  yaha_session_junction_params(yaha_session *s, ygpu_junction_params *p);
 /* ---- BGZF compression on the device (-obh / -obs: BAM output; device/bgzf.hip, csrc/bgzf_core.h) ---------------------------------------------------------

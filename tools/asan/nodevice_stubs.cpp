@@ -44,6 +44,9 @@ int  ygpu_pileup_gather(ygpu_ctx *, const uint32_t *, uint64_t, uint32_t *) { re
 int  ygpu_indels_enable(ygpu_ctx *, const ygpu_indel_params *) { return YGPU_ENODEV; }
 int  ygpu_indels_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
 int  ygpu_indels_collect(ygpu_ctx *, ygpu_indel_entry *, uint64_t *) { return YGPU_ENODEV; }
+int  ygpu_eprofile_enable(ygpu_ctx *, const ygpu_eprofile_params *) { return YGPU_ENODEV; }
+int  ygpu_eprofile_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
+int  ygpu_eprofile_collect(ygpu_ctx *, uint64_t *, uint64_t *) { return YGPU_ENODEV; }
 int  ygpu_junctions_enable(ygpu_ctx *, const ygpu_junction_params *) { return YGPU_ENODEV; }
 int  ygpu_junctions_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
 int  ygpu_junctions_collect(ygpu_ctx *, ygpu_junction *, uint64_t *) { return YGPU_ENODEV; }

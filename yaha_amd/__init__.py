@@ -129,6 +129,15 @@ class IndelEntry(C.Structure):
 INDEL_STATS = ("records_counted", "records_skipped_mapq", "records_dropped_two_sequences", "events", "reads_left_to_host", "events_lost")
 
 
+class EProfileParams(C.Structure):
+    _fields_ = [("min_mapq", C.c_uint32), ("n_seqs", C.c_uint32), ("seq_start", C.c_void_p), ("seq_length", C.c_void_p)]
+
+
+EPROFILE_WORDS = 1556
+# the sections of the table (yaha_amd/csrc/eprofile_core.h): name -> (first word, shape)
+EPROFILE_SECTIONS = {"SUB": (0, (5, 5)), "INS": (25, (65,)), "DEL": (90, (65,)), "IDENT": (155, (1001,)), "POS": (1156, (100, 4))}
+
+
 class JunctionParams(C.Structure):
     _fields_ = [("min_mapq", C.c_uint32), ("n_seqs", C.c_uint32), ("seq_start", C.c_void_p), ("seq_length", C.c_void_p)]
 
@@ -165,6 +174,7 @@ EXPORTS = (
     "ygpu_pileup_enable", "ygpu_pileup_size", "ygpu_pileup_collect", "ygpu_pileup_candidates_size", "ygpu_pileup_candidates_collect", "ygpu_pileup_gather",
     "yaha_session_pileup_params",
     "ygpu_indels_enable", "ygpu_indels_size", "ygpu_indels_collect", "yaha_session_indel_params",
+    "ygpu_eprofile_enable", "ygpu_eprofile_size", "ygpu_eprofile_collect", "yaha_session_eprofile_params",
     "ygpu_junctions_enable", "ygpu_junctions_size", "ygpu_junctions_collect", "yaha_session_junction_params",
     "ygpu_bgzf_open", "ygpu_bgzf_bound", "ygpu_bgzf_compress", "ygpu_bgzf_last_error", "ygpu_bgzf_close",
     "ygpu_bamsort_open", "ygpu_bamsort_append", "ygpu_bamsort_sort", "ygpu_bamsort_next", "ygpu_bamsort_info", "ygpu_bamsort_last_error", "ygpu_bamsort_close",
@@ -436,6 +446,22 @@ class Context:
         table is empty afterwards (ygpu_indels_collect)."""
         out, n, st = self._collect(lib().ygpu_indels_size, lib().ygpu_indels_collect, lambda n: ((IndelEntry * max(1, n))(),) * 2, INDEL_STATS)
         return [out[i] for i in range(n)], st
+
+    def eprofile_enable(self, session):
+        """The error profile of the printed clumps behind postfilter() (ygpu_eprofile_enable), in a table of this context's own, with the session's -epq and
+        sequence table.  After set_postfilter()."""
+        self._enable(lib().yaha_session_eprofile_params, lib().ygpu_eprofile_enable, EProfileParams(), session)
+
+    def eprofile_collect(self):
+        """(this context's table as it stands -- numpy uint64 of EPROFILE_WORDS words, sections EPROFILE_SECTIONS -- and the statistics as a dict); nothing is
+        cleared (ygpu_eprofile_collect)."""
+        import numpy as np
+
+        def make(n):
+            a = np.zeros(max(1, n), dtype=np.uint64)
+            return a, a.ctypes.data_as(C.POINTER(C.c_uint64))
+        words, n, st = self._collect(lib().ygpu_eprofile_size, lib().ygpu_eprofile_collect, make, DEPTH_STATS)
+        return words[:n], st
 
     def junctions_enable(self, session):
         """Split-read junctions of every batch behind postfilter() (ygpu_junctions_enable), with the session's -bpq and sequence table.  After set_postfilter()."""

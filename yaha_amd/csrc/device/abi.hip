@@ -364,6 +364,7 @@ std::vector<DevBuf *> allBuffers(ygpu_ctx *ctx)
                              &ctx->oqThr, &ctx->oqSeqStart, &ctx->oqSeqLen, &ctx->oqNeed, &ctx->oqPoolOff, &ctx->oqKeys, &ctx->oqStack, &ctx->oqNodes, &ctx->oqPrim, &ctx->oqPA,
                              &ctx->oqPfx, &ctx->oqPath, &ctx->oqPool, &ctx->oqPush, &ctx->oqOut, &ctx->oqOutCnt, &ctx->oqOutOps, &ctx->oqPrimCnt, &ctx->oqOutStart,
                              &ctx->oqOpsStart, &ctx->oqFClumps, &ctx->oqFOps, &ctx->jnCnt, &ctx->jnStart, &ctx->jnOut, &ctx->jnStats, &ctx->jnSeqStart, &ctx->jnSeqLen,
+                         &ctx->epTable, &ctx->epSeqs,
                          &ctx->puFwd, &ctx->puReadOff, &ctx->puTileCnt, &ctx->puTileStart, &ctx->puCand, &ctx->puSlots, &ctx->puRows,
                          &ctx->idTable, &ctx->idStats, &ctx->idSeqStart, &ctx->idSeqLen, &ctx->idBinBase, &ctx->idTileCnt, &ctx->idTileStart, &ctx->idOut};
     return std::vector<DevBuf *>(all, all + sizeof all / sizeof all[0]);
@@ -446,7 +447,8 @@ int ygpu_presize(ygpu_ctx *ctx, const ygpu_arena_profile *prof)
     for (size_t k = 0; k < all.size(); k++) {
         DevBuf *b = all[k];
         if (b == &ctx->dBases || b == &ctx->dSO || b == &ctx->dROA || b == &ctx->dLow || b == &ctx->counters || b == &ctx->ctr || b == &ctx->errFlag
-            || b == &ctx->pf.counters || b == &ctx->idTable || b == &ctx->idStats) continue;      // (the indel table is made, and zeroed, by its enable alone)
+            || b == &ctx->pf.counters || b == &ctx->idTable || b == &ctx->idStats || b == &ctx->epTable || b == &ctx->epSeqs) continue;      // (the indel table and the error
+                                                                                       // profile's are made, and zeroed, by their enables alone)
         if (prof->cap[k] > b->cap && b->ensureExact((size_t)prof->cap[k])) { (void)hipGetLastError(); ctx->err = "hipMalloc failed while presizing the arenas"; return YGPU_ENOMEM;
             }
     }

@@ -220,6 +220,11 @@ struct ygpu_ctx {
     bool idSet = false, idAuto = false;
     uint64_t idCap = 0, snapBases = 0;
     uint32_t idMinMapq = 0, idMinLen = 1, idNSeqs = 0, idUsed = 0;
+    // the error profile (-oep; eprofile_stage.h, ../eprofile_core.h): the context's own table -- YGPU_EPROFILE_WORDS uint64 words, then the four statistics
+    // words -- and the sequence table of its gate (starts, then lengths).  The stage reads the bases from puFwd / puReadOff as the pileup does.
+    DevBuf epTable, epSeqs;
+    bool epSet = false;
+    uint32_t epMinMapq = 0, epNSeqs = 0;
     // split-read junctions (-obp; junction_stage.h, ../junction_core.h): made per batch behind the post-filter, in buffers of the context's own -- counts and
     // their exclusive sums per read, the junctions (sized from the batch's filtered clump count), four statistics words, a sequence table of their own
     DevBuf jnCnt, jnStart, jnOut, jnStats, jnSeqStart, jnSeqLen;

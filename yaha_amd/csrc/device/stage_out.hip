@@ -3,13 +3,15 @@
 // ygpu_depth_enable asked for it, the read-depth track of the printed clumps (depth_stage.h), and when ygpu_events_enable did, their evidence track
 // (events_stage.h), and when ygpu_pileup_enable did, their allele pileup (pileup_stage.h: the one track that reads the reads' bases, which the snapshot then copies
 // as well), and when ygpu_indels_enable did, their indel alleles in the context's own hash table (indel_stage.h); and when ygpu_junctions_enable did, the
-// batch's split-read junctions (junction_stage.h), which leave with the filtered batch.
+// batch's split-read junctions (junction_stage.h), which leave with the filtered batch; and when ygpu_eprofile_enable did, their error profile in the context's
+// own table of counters (eprofile_stage.h).
 #include "ctx.h"
 #include "oqc_stage.h"
 #include "depth_stage.h"
 #include "events_stage.h"
 #include "pileup_stage.h"
 #include "indel_stage.h"
+#include "eprofile_stage.h"
 #include "junction_stage.h"
 #include <map>
 #include <tuple>
@@ -86,10 +88,10 @@ int ygpu_postfilter_snapshot(ygpu_ctx *ctx)
     if (n) KL(k_oqc_seeds, dim3(gridFor(n, 256)), dim3(256), 0, ctx->stream, ctx->dFwd.as<uint8_t>(), ctx->dReadOff.as<uint32_t>(), n, ctx->oqSeeds.as<uint32_t>(),
         ctx->oqQlen.as<uint32_t>());
     // the allele pileup reads the reads' bases behind the filter, when the next upload may have overwritten them: the forward codes (the reverse strand's channel
-    // follows from them, pileup_core.h) and the reads' offsets join the snapshot -- only on a context that enabled the pileup or the indel alleles, which read
-    // the inserted bases there
+    // follows from them, pileup_core.h) and the reads' offsets join the snapshot -- only on a context that enabled the pileup, the indel alleles, which read
+    // the inserted bases there, or the error profile, which reads every aligned base
     ctx->snapBases = ctx->totalBases;
-    if ((ctx->track[TRACK_PILEUP] || ctx->idSet) && n) {
+    if ((ctx->track[TRACK_PILEUP] || ctx->idSet || ctx->epSet) && n) {
         ENSURE(ctx->puFwd, ctx->totalBases + 1); ENSURE(ctx->puReadOff, 4ull * (n + 1));
         if (ctx->totalBases) HIPCHK(hipMemcpyAsync(ctx->puFwd.p, ctx->dFwd.p, ctx->totalBases, hipMemcpyDeviceToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(ctx->puReadOff.p, ctx->dReadOff.p, 4ull * (n + 1), hipMemcpyDeviceToDevice, ctx->stream));
@@ -172,6 +174,13 @@ static int launchTracks(ygpu_ctx *full, uint32_t n, uint32_t nClumps)
         A.stats = full->idStats.as<unsigned long long>(); A.used = full->idStats.as<uint32_t>() + 16; A.lost = A.used + 1;
         A.fwd = full->puFwd.as<uint8_t>(); A.readOff = full->puReadOff.as<uint32_t>();
         KL(k_indel_clumps, grid, block, 0, ctx->stream, A, fClumps, fOps, full->oqOutStart.as<uint32_t>(), n, nClumps);
+    }
+    // the error profile, last: a persistent grid, the table in LDS, into the context's own table (eprofile_stage.h)
+    if (full->epSet && full->epTable.p) {
+        EProfileArgs E; E.L = ydepth::Layout{full->epSeqs.as<uint32_t>(), full->epSeqs.as<uint32_t>() + full->epNSeqs, nullptr, full->epNSeqs, 1u, full->epMinMapq};
+        E.table = full->epTable.as<unsigned long long>(); E.bases = full->dBases.as<uint8_t>(); E.nBaseBytes = full->dBases.cap;
+        E.fwd = full->puFwd.as<uint8_t>(); E.readOff = full->puReadOff.as<uint32_t>();
+        KL(k_eprofile_clumps, dim3(eprofileGrid(nClumps)), dim3(64u * YE_WAVES), 0, ctx->stream, E, fClumps, fOps, full->oqOutStart.as<uint32_t>(), n, nClumps);
     }
     return 0;
 }
@@ -279,7 +288,7 @@ static int postfilterBody(ygpu_ctx *full)
     // the indel table by the rule: a batch larger than any before it gets a larger table while the table is empty (a table with entries stays as it is)
     if (full->idSet && full->idAuto && full->idUsed == 0 && full->idTable.p && yindel::tableCapacity(full->snapBases) > full->idCap) {
         rc = indelTable(full, yindel::tableCapacity(full->snapBases)); if (rc) return rc; }
-    // the binned tracks that are enabled (-oev, -ocov, -opu) and the indel alleles (-oid), behind the junctions on this stage's stream
+    // the binned tracks that are enabled (-oev, -ocov, -opu), the indel alleles (-oid) and the error profile (-oep), behind the junctions on this stage's stream
     rc = launchTracks(full, n, tot[0]); if (rc) return rc;
     // the indel table's used and lost words: one more small wait, behind the kernel.  An event that found no entry is an error of this call, not a fault.
     if (full->idSet && full->idTable.p && tot[0]) {
@@ -550,6 +559,54 @@ int ygpu_indels_collect(ygpu_ctx *full, ygpu_indel_entry *out, uint64_t stats[6]
     tlsPfFailed = nullptr;
     full->idUsed = 0;
     if (stats) { for (int k = 0; k < 5; k++) stats[k] = h[k]; stats[5] = (uint32_t)(h[8] >> 32); }
+    return 0;
+}
+// ---- the error profile (eprofile_stage.h; the contract is in ../eprofile_core.h) ------------------------------------------------------------------------------
+// Per context, as the indel alleles are: a table of the context's own, fed by every ygpu_postfilter, read (not cleared) by ygpu_eprofile_collect.
+int ygpu_eprofile_enable(ygpu_ctx *full, const ygpu_eprofile_params *p)
+{
+    if (!full || !full->stream || !p) return YGPU_EINVAL;
+    tlsPfFailed = nullptr;
+    if (!full->oqSet) { full->err = "ygpu_eprofile_enable: ygpu_set_postfilter has not been called on this context (the profile is counted behind the post-filter)";
+        return YGPU_EINVAL; }
+    if (!p->n_seqs || !p->seq_start || !p->seq_length || p->min_mapq > 255) { full->err = "ygpu_eprofile_enable: bad mapping quality or sequence table"; return YGPU_EINVAL; }
+    if (full->parked) { full->err = "ygpu_eprofile_enable: the context was parked (ygpu_park)"; return YGPU_EINVAL; }
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    HIPCHK(streamSync(ctx));                                                   // (a second enable: nothing of this side may still be using the table)
+    full->epSet = false;
+    ENSURE(full->epTable, 8ull * YE_LDS_WORDS); ENSURE(full->epSeqs, 8ull * p->n_seqs);
+    HIPCHK(hipMemsetAsync(full->epTable.p, 0, 8ull * YE_LDS_WORDS, ctx->stream));
+    HIPCHK(hipMemcpyAsync(full->epSeqs.p, p->seq_start, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(full->epSeqs.as<uint32_t>() + p->n_seqs, p->seq_length, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(streamSync(ctx));
+    tlsPfFailed = nullptr;
+    full->epMinMapq = p->min_mapq; full->epNSeqs = p->n_seqs; full->epSet = true;
+    return 0;
+}
+int ygpu_eprofile_size(ygpu_ctx *ctx, uint64_t *n_words)
+{
+    if (!ctx || !n_words) return YGPU_EINVAL;
+    if (!ctx->epSet) { ctx->err = "ygpu_eprofile_size: ygpu_eprofile_enable has not been called on this context"; return YGPU_EINVAL; }
+    *n_words = YGPU_EPROFILE_WORDS; return 0;
+}
+// The context's table as it stands: every filter stage queued on this context's post-filter side so far has finished when the copy is taken.
+int ygpu_eprofile_collect(ygpu_ctx *full, uint64_t *words, uint64_t stats[4])
+{
+    if (!full || !full->stream) return YGPU_EINVAL;
+    tlsPfFailed = nullptr;
+    if (!full->epSet) { full->err = "ygpu_eprofile_collect: ygpu_eprofile_enable has not been called on this context"; return YGPU_EINVAL; }
+    unsigned long long h[YE_LDS_WORDS]; memset(h, 0, sizeof h);
+    if (full->epTable.p) {                                                     // (parked: the table went with the arenas -- a parked context never ran a batch)
+        PfSide *ctx = &full->pf;
+        tlsPfFailed = full;
+        HIPCHK(hipSetDevice(full->device));
+        HIPCHK(hipMemcpyAsync(h, full->epTable.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
+        tlsPfFailed = nullptr;
+    }
+    if (words) for (uint32_t k = 0; k < (uint32_t)yeprofile::WORDS; k++) words[k] = h[k];
+    if (stats) for (uint32_t k = 0; k < 4; k++) stats[k] = h[yeprofile::WORDS + k];
     return 0;
 }
 // ---- split-read junctions (junction_stage.h; the contract is in ../junction_core.h) --------------------------------------------------------------------------

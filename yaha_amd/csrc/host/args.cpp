@@ -5,7 +5,8 @@
 // -ocov FILE / -covbin B / -covq Q (read depth of the printed records as bedGraph), -oev FILE / -evbin B / -evq Q / -evclip N (their mismatches, indels and
 // clipped ends per bin), -obp FILE / -bpq Q / -bpw W (split-read breakpoint calls as BEDPE), -opu FILE / -pumin N / -puq Q (the allele pileup: the sites where
 // at least N reads disagree with the reference, with the counts of A C G T N del ins), -oid FILE / -idmin N / -idlen L / -idq Q (indel alleles: position,
-// length and inserted bases of the insertions and deletions at least N printed records carry).
+// length and inserted bases of the insertions and deletions at least N printed records carry), -oep FILE / -epq Q (the error profile of the printed records:
+// substitution spectrum, indel lengths, identity, errors by position in the read).
 #include "yaha_host.h"
 #include <cstring>
 #include <cstdlib>
@@ -63,7 +64,14 @@ static void usage(FILE *o)
           "       chrom, position (1-based: a deletion's first deleted base, an insertion's next reference base), DEL or INS, length, the inserted bases as the\n"
           "       reference strand shows them (the first 42, then '+'; '*' for a deletion), records -- in index order, written after the last alignment.  Counted\n"
           "       on the device behind its post-filter in a hash table per context (32 bytes an entry, two entries per base of a batch: 1 GB at the default\n"
-          "       batch), which the host drains whenever a quarter of it is in use.  Errors in these four options leave with exit code 2.\n", o);
+          "       batch), which the host drains whenever a quarter of it is in use.  Errors in these four options leave with exit code 2.\n"
+          "  errors  : [-oep profileFile|stdout] [-epq minMapQ (0)]\n"
+          "       how good the printed records are, tab-separated, every line with its section's name first, written after the last alignment: SUB -- aligned\n"
+          "       bases by reference base (rows) and read base (columns), A C G T N --, INS and DEL -- insertions and deletions by length, 1 to 65+ --, IDENT --\n"
+          "       records by identity in per mille: matching bases / (aligned + inserted + deleted bases) --, POS -- aligned bases, those that differ, insertions\n"
+          "       and deletions by position in the read as sequenced, in hundredths of its length.  The first line has the records counted, left out by -epq\n"
+          "       and dropped.  Counted on the device behind its post-filter, in a table of 12 KB per context.  Errors in these two options leave with exit\n"
+          "       code 3.\n", o);
 }
 
 static bool parseBool(const char *s, const char *key, bool &out)
@@ -86,7 +94,7 @@ static bool parseFloat(const char *s, const char *key, float &out)
 }
 
 // (parseArgs returns the exit code + 1: the pileup's argument errors leave with 3 -- as its specification asks, and as the usage text says; the older tracks'
-// leave with 2)
+// leave with 2; the error profile's with 3 as well)
 static const int kPileupError = 4;
 
 int parseArgs(int argc, char **argv, Args &a)
@@ -182,6 +190,10 @@ int parseArgs(int argc, char **argv, Args &a)
             if (a.idLen < 1) { fprintf(stderr, "-idlen must be at least 1 (inserted or deleted bases).\n\n"); usage(stderr); return 3; } }
         else if (is("-idq")) { if (!parseInt(val(), "-idq", a.idMinQ)) return 3; a.haveIdQ = true;
             if (a.idMinQ < 0 || a.idMinQ > 255) { fprintf(stderr, "-idq must be a mapping quality (0 to 255).\n\n"); usage(stderr); return 3; } }
+        else if (is("-oep")) { const char *v = val(); a.epFileName = (!strcmp(v, "-stdout")) ? "stdout" : v; a.haveEp = true;
+            if (a.epFileName.empty()) { fprintf(stderr, "-oep needs a file name.\n\n"); usage(stderr); return kPileupError; } }
+        else if (is("-epq")) { if (!parseInt(val(), "-epq", a.epMinQ)) return kPileupError; a.haveEpQ = true;
+            if (a.epMinQ < 0 || a.epMinQ > 255) { fprintf(stderr, "-epq must be a mapping quality (0 to 255).\n\n"); usage(stderr); return kPileupError; } }
         else { fprintf(stderr, "%s is not a valid option.\n\n", k); usage(stderr); return 2; }
     }
     a.query = query; a.index = index && !query;
@@ -219,6 +231,14 @@ int parseArgs(int argc, char **argv, Args &a)
     if (a.haveId && a.idFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout") || (a.haveBp && a.bpFileName == "stdout")
         || (a.havePu && a.puFileName == "stdout"))) {
         fprintf(stderr, "-oid stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
+    // the error profile: the same rules, with the pileup's exit code (3)
+    if (!a.haveEp && a.haveEpQ) { fprintf(stderr, "-epq needs -oep.\n\n"); usage(stderr); return kPileupError; }
+    if (a.haveEp && !query) { fprintf(stderr, "-oep is an output of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return kPileupError; }
+    if (a.haveEp && a.epFileName == "stdout" && (!a.haveO || a.ofileName == "stdout")) {
+        fprintf(stderr, "-oep stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
+    if (a.haveEp && a.epFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout") || (a.haveBp && a.bpFileName == "stdout")
+        || (a.havePu && a.puFileName == "stdout") || (a.haveId && a.idFileName == "stdout"))) {
+        fprintf(stderr, "-oep stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
     // the sorted BAM: an option of -obh / -obs with a file of its own beside theirs
     if (a.haveSortMem && !a.bamSort) { fprintf(stderr, "-sortmem needs -obsort.\n\n"); usage(stderr); return 3; }
     if (a.bamSort && !query) { fprintf(stderr, "-obsort is an option of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return 3; }
@@ -295,6 +315,7 @@ std::string samHeader(const Args &a, const Genome &g)                   // outpu
     if (a.haveBp) { snprintf(buf, sizeof buf, " -bpq %d -bpw %d", a.bpMinQ, a.bpWindow); h += " -obp " + a.bpFileName + buf; }
     if (a.havePu) { snprintf(buf, sizeof buf, " -pumin %d -puq %d", a.puMinAlt, a.puMinQ); h += " -opu " + a.puFileName + buf; }
     if (a.haveId) { snprintf(buf, sizeof buf, " -idmin %d -idlen %d -idq %d", a.idMin, a.idLen, a.idMinQ); h += " -oid " + a.idFileName + buf; }
+    if (a.haveEp) { snprintf(buf, sizeof buf, " -epq %d", a.epMinQ); h += " -oep " + a.epFileName + buf; }
     h += "\n";
     return h;
 }

@@ -28,7 +28,7 @@ namespace yaha {
 
 // ---- what a run writes ------------------------------------------------------------------------------------------------------------------------------------------
 // The side outputs the options ask for, in the order their files are written in and their keys stand in the stats line: the binned tracks (depth.cpp,
-// events.cpp, pileup.cpp), the breakpoint calls (junctions.cpp), the indel alleles (indels.cpp).  A new kind is one line here.
+// events.cpp, pileup.cpp), the breakpoint calls (junctions.cpp), the indel alleles (indels.cpp), the error profile (eprofile.cpp).  A new kind is one line here.
 static std::vector<std::unique_ptr<SideOutput>> makeSideOutputs(const Args &a)
 {
     std::vector<std::unique_ptr<SideOutput>> o;
@@ -37,6 +37,7 @@ static std::vector<std::unique_ptr<SideOutput>> makeSideOutputs(const Args &a)
     if (a.havePu) o.emplace_back(new PileupTrack);
     if (a.haveBp) o.emplace_back(new JunctionTrack);
     if (a.haveId) o.emplace_back(new IndelTrack);
+    if (a.haveEp) o.emplace_back(new EProfileTrack);
     return o;
 }
 // (the main output -- SAM / Blast8 text, BAM, sorted BAM -- is makeRecordSink's choice, bam.cpp)

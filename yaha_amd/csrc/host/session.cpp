@@ -93,6 +93,11 @@ int yaha_session_indel_params(yaha_session *s, ygpu_indel_params *p)
     memset(p, 0, sizeof *p); sessionParams(s, p);
     p->min_mapq = (uint32_t)s->args.idMinQ; p->min_length = (uint32_t)s->args.idLen; return 0;
 }
+int yaha_session_eprofile_params(yaha_session *s, ygpu_eprofile_params *p)
+{
+    if (sessionParams(s, p) != 0) return YGPU_EINVAL;
+    p->min_mapq = (uint32_t)s->args.epMinQ; return 0;
+}
 int yaha_session_junction_params(yaha_session *s, ygpu_junction_params *p)
 {
     if (sessionParams(s, p) != 0) return YGPU_EINVAL;

@@ -89,6 +89,8 @@ struct Args {
     bool havePu = false, havePuMin = false, havePuQ = false; std::string puFileName; int puMinAlt = 2, puMinQ = 0;
     // indel alleles: -oid FILE (one line per insertion / deletion allele that at least -idmin printed records carry), -idlen L (shortest op counted), -idq Q
     bool haveId = false, haveIdMin = false, haveIdLen = false, haveIdQ = false; std::string idFileName; int idMin = 2, idLen = 1, idMinQ = 0;
+    // error profile: -oep FILE (substitution spectrum, indel lengths, identity of the records, errors by position in the read, of the printed records), -epq Q
+    bool haveEp = false, haveEpQ = false; std::string epFileName; int epMinQ = 0;
     bool query = false, index = true, compress = false, uncompress = false;   // -c / -u: .fa -> .nib2 / .nib2 -> .fasta only (Main.c:284-293, non-user builds of the reference)
 };
 void postProcessArgs(Args &a, bool query);                                  // AlignArgs.c:108-169
@@ -391,6 +393,33 @@ struct IndelTrack : SideOutput {
     bool write(const char *path, const Genome &g, std::string &err);      // applies minCount; path "stdout" = standard output
   private:
     int drainAbove(ygpu_ctx *ctx, uint64_t more, uint64_t limit);         // drains the table if it holds entries and they, with `more`, pass limit
+    const Genome *genome = nullptr; std::string file; std::vector<CtxAt> enabled;
+};
+
+// ---- the error profile (-oep; eprofile.cpp, ../eprofile_core.h) -----------------------------------------------------------------------------------------------
+// The run's table of 1556 counters -- substitutions by reference and read base, insertion and deletion lengths, the records' identity, pairs / errors /
+// insertions / deletions by position in the read -- and its writer.  The device keeps a table per context behind its post-filter (ygpu_eprofile_*: in LDS for a
+// workgroup's whole share of a batch), read once at the end of the run; the formatter threads count what the device did not -- runs whose post-filter stays on
+// the host, the reads it hands back unfiltered, builds without the entry points, YAHA_HOST_EPROFILE -- with the same walk (eprofile_core.h) into the batch's
+// slot, added here under a lock once per batch.
+struct EProfileTrack : SideOutput {
+    SeqTable seqs; uint32_t minMapq = 0;
+    std::mutex mu; std::vector<uint64_t> table;                           // the host's share while the run lasts (under mu), the whole run's after finish
+    uint64_t hostRecords = 0, hostSkipped = 0, hostDropped = 0;           // (under mu, by endBatch)
+    uint64_t devRecords = 0, devSkipped = 0, devDropped = 0, devHandedBack = 0;
+    // what a formatter thread gathers of one batch before it merges: a table of its own and what became of the records it walked
+    struct Local : Slot { std::vector<uint64_t> words; uint64_t records = 0, skipped = 0, dropped = 0; };
+    const char *name() const override { return "-oep"; }
+    bool setup(const Args &a, const Genome &g, int nImages, int nContexts, std::string &err) override;      // -epq
+    int  enable(const CtxAt &at) override;                                // (remembers the context for the end of the run)
+    Slot *newSlot() const override;
+    void add(const OutClump &oc, const Read &r, Slot *s) override;        // one record printClump was called for
+    void endBatch(Slot *s) override;                                      // ... and the batch's share into the run's table; clears the slot
+    bool finish(FILE *mainOut, FILE *log, bool timing) override;          // every enabled context's table, then the file
+    void stats(std::string &line) const override;
+    static bool deviceEntryPoints();                                      // does this build have ygpu_eprofile_*?
+    bool write(const char *path, std::string &err) const;                 // path "stdout" = standard output
+  private:
     const Genome *genome = nullptr; std::string file; std::vector<CtxAt> enabled;
 };
 
