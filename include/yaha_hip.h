@@ -297,6 +297,37 @@ int  ygpu_pileup_candidates_collect(ygpu_ctx *ctx, uint32_t *slots);           /
 /* rows[n * 7]: the seven counts of slots[0 .. n) (host memory; ascending for locality, not checked; a slot past the array reads as zeros). */
 int  ygpu_pileup_gather(ygpu_ctx *ctx, const uint32_t *slots, uint64_t n, uint32_t *rows);
 
+/* ---- SNV calls with genotypes from the pileup array (optional; needs ygpu_pileup_enable) -----------------------------------------------------------------------
+ * The step behind the pileup: which allele the reads carry at a slot, how sure that is, and whether the sample is heterozygous there -- judged on the device,
+ * one selection pass over the image's array, so that only the calls cross PCIe.  The contract (yaha_amd/csrc/snv_core.h -- one set of routines for host and
+ * device): r = the count of the reference's own base, a = the greatest count among the other three of A C G T (ties to the lowest channel), D = A + C + G + T,
+ * other = N + DEL; PL0 = r cost_match + a cost_error, PL1 = (r + a) cost_het, PL2 = r cost_error + a cost_match in 1/100 phred, GT the smallest (ties to the
+ * lower index), QUAL = min(PL0 - least, 999 900) / 100, GQ = min(second smallest - least, 9 900) / 100; a slot is a call when GT != 0, a >= min_alt,
+ * D >= min_depth and QUAL >= min_qual.  A slot whose reference base is not one of A C G T is never a call.  The three costs come from the caller: the device
+ * takes no logarithm (yaha_session_snv_params derives them from -snverr; 46, 1477 and 331 at the default of 100 per mille).
+ * One call needs the SUM of all sources before it is judged -- the counts the caller made itself (reads handed back unfiltered, runs filtered on the host), the
+ * other index images of a run over several devices.  ygpu_pileup_add folds such a source into ONE image's array: rows[i * 7 + channel] is added to slot
+ * slots[i] with global atomics; a slot at or past n_slots adds nothing; slots need not be distinct or ordered.  An array folded into is no longer the image's
+ * own counts: nothing may read it as such afterwards.
+ * ygpu_snv_call_size runs the selection over the array as it stands (a wave per tile of 2 048 slots, the tiles' counts through the exclusive sum, the records
+ * written by ballot and population count in ascending slot order, no atomics) and returns the number of calls; ygpu_snv_collect copies the records of the last
+ * selection.  A second ygpu_snv_call_size, with other parameters, selects again over the same array.  Like the candidates, these calls wait for everything
+ * queued on the device, use the post-filter's side of the context and serve a parked context. */
+typedef struct ygpu_snv_params {
+    uint32_t cost_match, cost_error, cost_het;          /* 1/100 phred: a read that shows the genotype's base / another base / one of a heterozygote's two */
+    uint32_t min_alt, min_depth, min_qual;              /* at least 1, at least 1, whole phred */
+    uint32_t reserved[2];                               /* zero */
+} ygpu_snv_params;
+/* 48 bytes.  info = channel of the reference's base | channel of alt << 4 | GT << 8 | the reference's 4-bit code << 12 (channels: A0 C1 G2 T3); depth and
+ * other saturate at 2^32 - 1; pl[3]: the three normalised likelihoods in 1/100 phred, each saturated at 2^32 - 1 */
+typedef struct ygpu_snv_call {
+    uint32_t slot, info, ref_count, alt_count, depth, other, qual, gq;
+    uint32_t pl[3], zero;
+} ygpu_snv_call;
+int  ygpu_pileup_add(ygpu_ctx *ctx, const uint32_t *slots, const uint32_t *rows, uint64_t n);      /* after ygpu_pileup_enable */
+int  ygpu_snv_call_size(ygpu_ctx *ctx, const ygpu_snv_params *p, uint64_t *n);                     /* selects; *n = calls of the array as it stands */
+int  ygpu_snv_collect(ygpu_ctx *ctx, ygpu_snv_call *calls);                                        /* calls[n] of the last ygpu_snv_call_size, ascending */
+
 /* ---- indel alleles: which insertions and deletions the printed alignments carry (optional, behind ygpu_postfilter) -----------------------------------------------
  * What the pileup's INS and DEL channels leave out: how long an indel is and what was inserted.  With ygpu_indels_enable, every ygpu_postfilter of the context
  * also counts the indel ALLELES of the clumps it returns in a hash table on the device.  The contract (yaha_amd/csrc/indel_core.h -- one set of routines for
@@ -498,6 +529,8 @@ int  yaha_session_depth_params(yaha_session *s, ygpu_depth_params *p);
 int  yaha_session_events_params(yaha_session *s, ygpu_events_params *p);
 /* The same for ygpu_pileup_enable: -puq (default 0) and the sequence table (pointers of their own into the session). */
 int  yaha_session_pileup_params(yaha_session *s, ygpu_pileup_params *p);
+/* For ygpu_snv_call_size: the three costs derived from -snverr (default 100 per mille), -snvmin (2), -snvdp (4) and -snvqual (20). */
+int  yaha_session_snv_params(yaha_session *s, ygpu_snv_params *p);
 /* The same for ygpu_indels_enable: -idq (default 0), -idlen (default 1), capacity 0 and the sequence table (pointers of their own into the session). */
 int  yaha_session_indel_params(yaha_session *s, ygpu_indel_params *p);
 /* The same for ygpu_eprofile_enable: -epq (default 0) and the sequence table (pointers of their own into the session). */

@@ -41,6 +41,9 @@ int  ygpu_pileup_collect(ygpu_ctx *, uint32_t *, uint64_t *) { return YGPU_ENODE
 int  ygpu_pileup_candidates_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
 int  ygpu_pileup_candidates_collect(ygpu_ctx *, uint32_t *) { return YGPU_ENODEV; }
 int  ygpu_pileup_gather(ygpu_ctx *, const uint32_t *, uint64_t, uint32_t *) { return YGPU_ENODEV; }
+int  ygpu_pileup_add(ygpu_ctx *, const uint32_t *, const uint32_t *, uint64_t) { return YGPU_ENODEV; }
+int  ygpu_snv_call_size(ygpu_ctx *, const ygpu_snv_params *, uint64_t *) { return YGPU_ENODEV; }
+int  ygpu_snv_collect(ygpu_ctx *, ygpu_snv_call *) { return YGPU_ENODEV; }
 int  ygpu_indels_enable(ygpu_ctx *, const ygpu_indel_params *) { return YGPU_ENODEV; }
 int  ygpu_indels_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
 int  ygpu_indels_collect(ygpu_ctx *, ygpu_indel_entry *, uint64_t *) { return YGPU_ENODEV; }

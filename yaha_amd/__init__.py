@@ -94,6 +94,16 @@ PILEUP_CHANNELS = ("A", "C", "G", "T", "N", "del", "ins")
 PILEUP_STATS = DEPTH_STATS + ("counts_added",)
 
 
+class SnvParams(C.Structure):
+    """The three costs in 1/100 phred and the three thresholds of a call (include/yaha_hip.h: ygpu_snv_params)."""
+    _fields_ = [("cost_match", C.c_uint32), ("cost_error", C.c_uint32), ("cost_het", C.c_uint32), ("min_alt", C.c_uint32), ("min_depth", C.c_uint32),
+                ("min_qual", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+# one call (ygpu_snv_call, 48 bytes): info = channel of the reference's base | channel of alt << 4 | GT << 8 | the reference's 4-bit code << 12
+SNV_CALL_FIELDS = ("slot", "info", "ref_count", "alt_count", "depth", "other", "qual", "gq", "pl0", "pl1", "pl2", "zero")
+
+
 class IndelParams(C.Structure):
     _fields_ = [("min_mapq", C.c_uint32), ("min_length", C.c_uint32), ("n_seqs", C.c_uint32), ("reserved", C.c_uint32), ("seq_start", C.c_void_p), ("seq_length", C.c_void_p),
                 ("capacity", C.c_uint64)]
@@ -173,6 +183,7 @@ EXPORTS = (
     "ygpu_events_enable", "ygpu_events_size", "ygpu_events_collect", "yaha_session_events_params",
     "ygpu_pileup_enable", "ygpu_pileup_size", "ygpu_pileup_collect", "ygpu_pileup_candidates_size", "ygpu_pileup_candidates_collect", "ygpu_pileup_gather",
     "yaha_session_pileup_params",
+    "ygpu_pileup_add", "ygpu_snv_call_size", "ygpu_snv_collect", "yaha_session_snv_params",
     "ygpu_indels_enable", "ygpu_indels_size", "ygpu_indels_collect", "yaha_session_indel_params",
     "ygpu_eprofile_enable", "ygpu_eprofile_size", "ygpu_eprofile_collect", "yaha_session_eprofile_params",
     "ygpu_junctions_enable", "ygpu_junctions_size", "ygpu_junctions_collect", "yaha_session_junction_params",
@@ -425,6 +436,31 @@ class Context:
         self._check(lib().ygpu_pileup_gather(self._h, sl.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_uint64(len(sl)), rows.ctypes.data_as(C.POINTER(C.c_uint32))),
                     "ygpu_pileup_gather")
         return rows[:len(sl)]
+
+    def pileup_add(self, slots, rows):
+        """Adds rows[i] (seven counts) to slot slots[i] of the image's array (ygpu_pileup_add): a slot past the array adds nothing, slots may repeat.  The array
+        then holds a sum of sources and is no longer the image's own counts."""
+        import numpy as np
+        sl = np.ascontiguousarray(slots, dtype=np.uint32); rw = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, len(PILEUP_CHANNELS))
+        if len(sl) != len(rw):
+            raise ValueError("pileup_add: %d slots, %d rows" % (len(sl), len(rw)))
+        self._check(lib().ygpu_pileup_add(self._h, sl.ctypes.data_as(C.POINTER(C.c_uint32)), rw.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_uint64(len(sl))),
+                    "ygpu_pileup_add")
+
+    def snv_calls(self, session_or_params):
+        """The SNV calls of the image's array as it stands, ascending by slot, selected and judged on the device (ygpu_snv_call_size / ygpu_snv_collect): a
+        structured numpy array with the fields SNV_CALL_FIELDS, all uint32.  The parameters: a SnvParams, or a Session whose options give them."""
+        import numpy as np
+        p = session_or_params
+        if not isinstance(p, SnvParams):
+            p = SnvParams()
+            if lib().yaha_session_snv_params(session_or_params._h, C.byref(p)) != 0:
+                raise RuntimeError("yaha_session_snv_params: " + lib().yaha_session_error(session_or_params._h).decode())
+        n = C.c_uint64()
+        self._check(lib().ygpu_snv_call_size(self._h, C.byref(p), C.byref(n)), "ygpu_snv_call_size")
+        out = np.zeros(max(1, n.value), dtype=np.dtype([(f, np.uint32) for f in SNV_CALL_FIELDS]))
+        self._check(lib().ygpu_snv_collect(self._h, out.ctypes.data_as(C.c_void_p)), "ygpu_snv_collect")
+        return out[:n.value]
 
     def indels_enable(self, session, capacity=0):
         """Indel alleles of the printed clumps behind postfilter() (ygpu_indels_enable), counted in a hash table of this context's own, with the session's -idq,

@@ -212,6 +212,10 @@ struct ygpu_ctx {
     // candidate slots, a caller's slot list and the rows gathered for it
     DevBuf puFwd, puReadOff, puTileCnt, puTileStart, puCand, puSlots, puRows;
     uint64_t puNCand = 0; bool puHaveCand = false;
+    // SNV calls (-osnv; snv_stage.h, ../snv_core.h): the records of the last selection over the image's pileup array (the tiles' counts and sums are the
+    // candidates' buffers, a fold's list and rows the gather's)
+    DevBuf snvOut;
+    uint64_t snvN = 0; bool snvHave = false;
     // indel alleles (-oid; indel_stage.h, ../indel_core.h): the context's own hash table (idCap entries of 32 bytes, a power of two; idAuto: sized by the rule and
     // made larger, while empty, before a larger batch), its statistics (eight 64-bit words, then the used and the lost word), the sequence table and slot bases
     // of its layout, and for draining the occupied entries per tile, their exclusive sums and the compacted entries.  The stage reads the bases from puFwd /

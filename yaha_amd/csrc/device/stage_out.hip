@@ -4,12 +4,13 @@
 // (events_stage.h), and when ygpu_pileup_enable did, their allele pileup (pileup_stage.h: the one track that reads the reads' bases, which the snapshot then copies
 // as well), and when ygpu_indels_enable did, their indel alleles in the context's own hash table (indel_stage.h); and when ygpu_junctions_enable did, the
 // batch's split-read junctions (junction_stage.h), which leave with the filtered batch; and when ygpu_eprofile_enable did, their error profile in the context's
-// own table of counters (eprofile_stage.h).
+// own table of counters (eprofile_stage.h).  At the end of a run the pileup array also gives the SNV calls (snv_stage.h: folds into it, the selection over it).
 #include "ctx.h"
 #include "oqc_stage.h"
 #include "depth_stage.h"
 #include "events_stage.h"
 #include "pileup_stage.h"
+#include "snv_stage.h"
 #include "indel_stage.h"
 #include "eprofile_stage.h"
 #include "junction_stage.h"
@@ -477,6 +478,78 @@ int ygpu_pileup_gather(ygpu_ctx *full, const uint32_t *slots, uint64_t n, uint32
         HIPCHK(hipMemcpyAsync(rows + at * ypileup::NCH, full->puRows.p, 4ull * ypileup::NCH * m, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(streamSync(ctx));
     }
+    tlsPfFailed = nullptr;
+    return 0;
+}
+// ---- SNV calls from the pileup array (snv_stage.h; the contract is in ../snv_core.h) -----------------------------------------------------------------------------
+// A source folded into the image's array: the caller's list and rows, a piece at a time through the gather's buffers, added with global atomics
+int ygpu_pileup_add(ygpu_ctx *full, const uint32_t *slots, const uint32_t *rows, uint64_t n)
+{
+    if (!full || !full->stream || (n && (!slots || !rows))) return YGPU_EINVAL;
+    if (!full->track[TRACK_PILEUP]) { full->err = "ygpu_pileup_add: ygpu_pileup_enable has not been called on this context"; return YGPU_EINVAL; }
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    HIPCHK(hipDeviceSynchronize());
+    const TrackImage &T = *full->track[TRACK_PILEUP];
+    const uint64_t piece = 1ull << 22;
+    for (uint64_t at = 0; at < n; at += piece) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(piece, n - at);
+        ENSURE(full->puSlots, 4ull * m); ENSURE(full->puRows, 4ull * ypileup::NCH * m);
+        HIPCHK(hipMemcpyAsync(full->puSlots.p, slots + at, 4ull * m, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(full->puRows.p, rows + at * ypileup::NCH, 4ull * ypileup::NCH * m, hipMemcpyHostToDevice, ctx->stream));
+        KL(k_pileup_add, dim3(gridFor((uint64_t)m * ypileup::NCH, 256)), dim3(256), 0, ctx->stream, T.data.as<uint32_t>(), (uint32_t)T.nBins,
+            full->puSlots.as<uint32_t>(), full->puRows.as<uint32_t>(), m);
+        HIPCHK(streamSync(ctx));                                               // (the caller's memory is pageable: the next piece may overwrite the buffers only now)
+    }
+    tlsPfFailed = nullptr;
+    return 0;
+}
+// The calls of the image's array as it stands, ascending -- the candidates' three steps (count a tile, exclusive sums, emit) with the verdict of snv_core.h in the
+// place of the site test; the tiles' counts and sums live in the candidates' buffers (a selection of either kind leaves the other's RESULT alone).
+int ygpu_snv_call_size(ygpu_ctx *full, const ygpu_snv_params *p, uint64_t *n)
+{
+    if (!full || !full->stream || !p || !n) return YGPU_EINVAL;
+    if (!full->track[TRACK_PILEUP]) { full->err = "ygpu_snv_call_size: ygpu_pileup_enable has not been called on this context"; return YGPU_EINVAL; }
+    if (p->min_alt < 1 || p->min_depth < 1) { full->err = "ygpu_snv_call_size: min_alt and min_depth must be at least 1"; return YGPU_EINVAL; }
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    HIPCHK(hipDeviceSynchronize());
+    const TrackImage &T = *full->track[TRACK_PILEUP];
+    full->snvHave = false; full->snvN = 0;
+    int rc = pileupSide(full); if (rc) return rc;
+    const uint32_t nSlots = (uint32_t)T.nBins, nTiles = (uint32_t)((T.nBins + YS_TILE - 1) / YS_TILE);
+    ENSURE(full->puTileCnt, 4ull * (nTiles + 2)); ENSURE(full->puTileStart, 4ull * (nTiles + 2));
+    HIPCHK(hipMemsetAsync((uint32_t *)full->puTileCnt.p + nTiles, 0, 8, ctx->stream));
+    SnvArgs A; A.L = trackLayout(T); A.pu = T.data.as<uint32_t>(); A.nSlots = nSlots; A.nTiles = nTiles;
+    A.bases = full->dBases.as<uint8_t>(); A.nBaseBytes = full->dBases.cap; A.P = *p;
+    A.cnt = full->puTileCnt.as<uint32_t>(); A.start = full->puTileStart.as<uint32_t>(); A.out = nullptr; A.cap = 0;
+    const dim3 grid(gridFor((uint64_t)nTiles * 64, 256));
+    KL(k_snv_count, grid, dim3(256), 0, ctx->stream, A);
+    rc = cubScan(ctx, full->puTileCnt.as<uint32_t>(), full->puTileStart.as<uint32_t>(), nTiles + 1); if (rc) return rc;
+    uint32_t tot = 0, scanFail = 0;
+    { const FetchPiece pc[2] = {{full->puTileStart.as<uint32_t>() + nTiles, &tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1}};
+      rc = fetchMany(ctx, pc, 2); if (rc) return rc; }
+    if (scanFail) return scanGaveUp(ctx, "SNV calls");
+    ENSURE(full->snvOut, sizeof(ygpu_snv_call) * ((uint64_t)tot + 1));
+    A.out = full->snvOut.as<ygpu_snv_call>(); A.cap = tot;
+    if (tot) KL(k_snv_emit, grid, dim3(256), 0, ctx->stream, A);
+    HIPCHK(streamSync(ctx));
+    tlsPfFailed = nullptr;
+    full->snvN = tot; full->snvHave = true; *n = tot;
+    return 0;
+}
+int ygpu_snv_collect(ygpu_ctx *full, ygpu_snv_call *calls)
+{
+    if (!full || !full->stream) return YGPU_EINVAL;
+    if (!full->snvHave || !full->snvOut.p) { full->err = "ygpu_snv_collect: ygpu_snv_call_size has not been called on this context"; return YGPU_EINVAL; }
+    if (!full->snvN) return 0;
+    if (!calls) return YGPU_EINVAL;
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    HIPCHK(hipMemcpyAsync(calls, full->snvOut.p, sizeof(ygpu_snv_call) * full->snvN, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
     tlsPfFailed = nullptr;
     return 0;
 }

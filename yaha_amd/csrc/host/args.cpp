@@ -6,7 +6,8 @@
 // clipped ends per bin), -obp FILE / -bpq Q / -bpw W (split-read breakpoint calls as BEDPE), -opu FILE / -pumin N / -puq Q (the allele pileup: the sites where
 // at least N reads disagree with the reference, with the counts of A C G T N del ins), -oid FILE / -idmin N / -idlen L / -idq Q (indel alleles: position,
 // length and inserted bases of the insertions and deletions at least N printed records carry), -oep FILE / -epq Q (the error profile of the printed records:
-// substitution spectrum, indel lengths, identity, errors by position in the read).
+// substitution spectrum, indel lengths, identity, errors by position in the read), -osnv FILE / -snverr E / -snvmin N / -snvdp D / -snvqual Q (SNV calls with
+// genotypes as VCF 4.2, judged on the device from the pileup array; their mapping-quality gate is -puq).
 #include "yaha_host.h"
 #include <cstring>
 #include <cstdlib>
@@ -71,7 +72,16 @@ static void usage(FILE *o)
           "       records by identity in per mille: matching bases / (aligned + inserted + deleted bases) --, POS -- aligned bases, those that differ, insertions\n"
           "       and deletions by position in the read as sequenced, in hundredths of its length.  The first line has the records counted, left out by -epq\n"
           "       and dropped.  Counted on the device behind its post-filter, in a table of 12 KB per context.  Errors in these two options leave with exit\n"
-          "       code 3.\n", o);
+          "       code 3.\n"
+          "  SNVs    : [-osnv callsFile|stdout] [-snverr errorPerMille (100)] [-snvmin minAltReads (2)] [-snvdp minDepth (4)] [-snvqual minQual (20)] [-puq minMapQ (0)]\n"
+          "       the sites where the pileup of the printed records says the sample differs from the reference, as VCF 4.2 with one sample, written after the last\n"
+          "       alignment: r reads show the reference's base, a the most frequent other base of A C G T; the genotypes 0/0, 0/1 and 1/1 cost r cM + a cE,\n"
+          "       (r + a) cH and r cE + a cM in 1/100 phred, the three costs derived from -snverr (46, 1477, 331 at 100); GT is the cheapest, QUAL what 0/0 costs\n"
+          "       more (at most 9999), GQ what the second cheapest costs more (at most 99).  A line needs GT 0/1 or 1/1, a >= -snvmin, A + C + G + T >= -snvdp and\n"
+          "       QUAL >= -snvqual.  Indels are not called (-oid holds them).  The counts are the pileup's (-opu; 28 bytes of device memory per reference base per\n"
+          "       GPU, made for -osnv alone as well, with -puq as its gate); the sites are judged on the device and only the calls leave it.  With -gpus N the\n"
+          "       other devices' candidate sites are added to the first one's array before that, which moves what -opu moves.  YAHA_HOST_SNV=1: judged on the\n"
+          "       host.  Errors in these five options leave with exit code 3.\n", o);
 }
 
 static bool parseBool(const char *s, const char *key, bool &out)
@@ -194,6 +204,15 @@ int parseArgs(int argc, char **argv, Args &a)
             if (a.epFileName.empty()) { fprintf(stderr, "-oep needs a file name.\n\n"); usage(stderr); return kPileupError; } }
         else if (is("-epq")) { if (!parseInt(val(), "-epq", a.epMinQ)) return kPileupError; a.haveEpQ = true;
             if (a.epMinQ < 0 || a.epMinQ > 255) { fprintf(stderr, "-epq must be a mapping quality (0 to 255).\n\n"); usage(stderr); return kPileupError; } }
+        else if (is("-osnv")) { const char *v = val(); a.snvFileName = (!strcmp(v, "-stdout")) ? "stdout" : v; a.haveSnv = true;
+            if (a.snvFileName.empty()) { fprintf(stderr, "-osnv needs a file name.\n\n"); usage(stderr); return kPileupError; } }
+        else if (is("-snverr")) { if (!parseInt(val(), "-snverr", a.snvErr)) return kPileupError; a.haveSnvErr = true;
+            if (a.snvErr < 1 || a.snvErr > 500) { fprintf(stderr, "-snverr must be between 1 and 500 (sequencing error in per mille).\n\n"); usage(stderr); return kPileupError; } }
+        else if (is("-snvmin")) { if (!parseInt(val(), "-snvmin", a.snvMin)) return kPileupError; a.haveSnvMin = true;
+            if (a.snvMin < 1) { fprintf(stderr, "-snvmin must be at least 1 (reads that carry the allele).\n\n"); usage(stderr); return kPileupError; } }
+        else if (is("-snvdp")) { if (!parseInt(val(), "-snvdp", a.snvDp)) return kPileupError; a.haveSnvDp = true;
+            if (a.snvDp < 1) { fprintf(stderr, "-snvdp must be at least 1 (reads that show A, C, G or T).\n\n"); usage(stderr); return kPileupError; } }
+        else if (is("-snvqual")) { if (!parseInt(val(), "-snvqual", a.snvQual)) return kPileupError; a.haveSnvQual = true; }
         else { fprintf(stderr, "%s is not a valid option.\n\n", k); usage(stderr); return 2; }
     }
     a.query = query; a.index = index && !query;
@@ -217,7 +236,7 @@ int parseArgs(int argc, char **argv, Args &a)
     if (a.haveBp && a.bpFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout"))) {
         fprintf(stderr, "-obp stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
     // the allele pileup: the same rules, its errors with an exit code of their own (3)
-    if (!a.havePu && (a.havePuMin || a.havePuQ)) { fprintf(stderr, "-pumin and -puq need -opu.\n\n"); usage(stderr); return kPileupError; }
+    if (!a.havePu && (a.havePuMin || (a.havePuQ && !a.haveSnv))) { fprintf(stderr, "-pumin needs -opu, -puq needs -opu or -osnv.\n\n"); usage(stderr); return kPileupError; }
     if (a.havePu && !query) { fprintf(stderr, "-opu is an output of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return kPileupError; }
     if (a.havePu && a.puFileName == "stdout" && (!a.haveO || a.ofileName == "stdout")) {
         fprintf(stderr, "-opu stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
@@ -239,6 +258,15 @@ int parseArgs(int argc, char **argv, Args &a)
     if (a.haveEp && a.epFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout") || (a.haveBp && a.bpFileName == "stdout")
         || (a.havePu && a.puFileName == "stdout") || (a.haveId && a.idFileName == "stdout"))) {
         fprintf(stderr, "-oep stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
+    // the SNV calls: the same rules, with the pileup's exit code (3); their mapping-quality gate is the pileup's -puq
+    if (!a.haveSnv && (a.haveSnvErr || a.haveSnvMin || a.haveSnvDp || a.haveSnvQual)) { fprintf(stderr, "-snverr, -snvmin, -snvdp and -snvqual need -osnv.\n\n"); usage(stderr);
+        return kPileupError; }
+    if (a.haveSnv && !query) { fprintf(stderr, "-osnv is an output of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return kPileupError; }
+    if (a.haveSnv && a.snvFileName == "stdout" && (!a.haveO || a.ofileName == "stdout")) {
+        fprintf(stderr, "-osnv stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
+    if (a.haveSnv && a.snvFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout") || (a.haveBp && a.bpFileName == "stdout")
+        || (a.havePu && a.puFileName == "stdout") || (a.haveId && a.idFileName == "stdout") || (a.haveEp && a.epFileName == "stdout"))) {
+        fprintf(stderr, "-osnv stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
     // the sorted BAM: an option of -obh / -obs with a file of its own beside theirs
     if (a.haveSortMem && !a.bamSort) { fprintf(stderr, "-sortmem needs -obsort.\n\n"); usage(stderr); return 3; }
     if (a.bamSort && !query) { fprintf(stderr, "-obsort is an option of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return 3; }
@@ -316,6 +344,7 @@ std::string samHeader(const Args &a, const Genome &g)                   // outpu
     if (a.havePu) { snprintf(buf, sizeof buf, " -pumin %d -puq %d", a.puMinAlt, a.puMinQ); h += " -opu " + a.puFileName + buf; }
     if (a.haveId) { snprintf(buf, sizeof buf, " -idmin %d -idlen %d -idq %d", a.idMin, a.idLen, a.idMinQ); h += " -oid " + a.idFileName + buf; }
     if (a.haveEp) { snprintf(buf, sizeof buf, " -epq %d", a.epMinQ); h += " -oep " + a.epFileName + buf; }
+    if (a.haveSnv) { snprintf(buf, sizeof buf, " -snverr %d -snvmin %d -snvdp %d -snvqual %d", a.snvErr, a.snvMin, a.snvDp, a.snvQual); h += " -osnv " + a.snvFileName + buf; }
     h += "\n";
     return h;
 }

@@ -42,12 +42,18 @@ int BinnedTrack::beforeFilter(const CtxAt &at, size_t)
     return 0;
 }
 
+void BinnedTrack::feeders(std::vector<ygpu_ctx *> &ctx, std::vector<int> &dev) const
+{
+    ctx.clear(); dev.clear();
+    for (auto &x : feeder) if (const int c1 = x.load()) { ctx.push_back(ctxs[c1 - 1].ctx); dev.push_back(ctxs[c1 - 1].device); }
+}
+
 // every image's array added to the host's, the file written after the last alignment
 bool BinnedTrack::finish(FILE *mainOut, FILE *log, bool timing)
 {
     auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     std::string terr; bool ok = true; std::vector<ygpu_ctx *> feedCtx; std::vector<int> feedDev;
-    for (auto &x : feeder) if (const int c1 = x.load()) { feedCtx.push_back(ctxs[c1 - 1].ctx); feedDev.push_back(ctxs[c1 - 1].device); }
+    feeders(feedCtx, feedDev);
     const double m0 = now();
     int failed = -1; const int rc = mergeDevices(feedCtx.data(), (int)feedCtx.size(), *genome, &failed, terr);
     const double m1 = now();

@@ -78,14 +78,12 @@ int PileupTrack::deviceEnable(ygpu_ctx *ctx) const
     return ygpu_pileup_enable(ctx, &p);
 }
 
-int PileupTrack::mergeDevices(ygpu_ctx *const *feeders, int n, const Genome &g, int *failed, std::string &err)
+int PileupTrack::candidatesUnion(ygpu_ctx *const *feeders, int n, bool withHost, const Genome &g, std::vector<uint32_t> &all, int *failed, std::string &err)
 {
     const ydepth::Layout L = layout();
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = now();
     // 1. every source's candidates: the host's blocks, then each image's selection
-    std::vector<uint32_t> all;
-    for (size_t b = 0; b < blocks.size(); b++) if (blocks[b]) {
+    all.clear();
+    if (withHost) for (size_t b = 0; b < blocks.size(); b++) if (blocks[b]) {
         const uint64_t s0 = (uint64_t)b * kBlock, s1 = std::min<uint64_t>(s0 + kBlock, nBins);
         for (uint64_t s = s0; s < s1; s++) if (ypileup::isSiteAt(L, g.bases, g.nBaseBytes, (uint32_t)s, row((uint32_t)s), 1u)) all.push_back((uint32_t)s);
     }
@@ -101,20 +99,37 @@ int PileupTrack::mergeDevices(ygpu_ctx *const *feeders, int n, const Genome &g, 
         merged.resize((size_t)(std::set_union(all.begin(), all.end(), mine.begin(), mine.end(), merged.begin()) - merged.begin()));
         all.swap(merged);
     }
-    nCandidates = all.size();
+    return 0;
+}
+
+int PileupTrack::unionRows(ygpu_ctx *const *feeders, int n, bool withHost, bool account, const Genome &g, std::vector<uint32_t> &all, std::vector<uint32_t> &rows,
+                           int *failed, std::string &err)
+{
+    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = now();
+    { const int rc = candidatesUnion(feeders, n, withHost, g, all, failed, err); if (rc != 0) return rc; }
     const double t1 = now(); msCandidates = t1 - t0;
     // 3. every image's counts at the union, 4. the host's own on top
-    std::vector<uint32_t> rows(all.size() * ypileup::NCH + 1, 0), part;
-    for (size_t i = 0; i < all.size(); i++) if (const uint32_t *own = row(all[i])) memcpy(rows.data() + i * ypileup::NCH, own, sizeof(uint32_t) * ypileup::NCH);
+    rows.assign(all.size() * ypileup::NCH + 1, 0); std::vector<uint32_t> part;
+    if (withHost) for (size_t i = 0; i < all.size(); i++) if (const uint32_t *own = row(all[i])) memcpy(rows.data() + i * ypileup::NCH, own, sizeof(uint32_t) * ypileup::NCH);
     for (int k = 0; k < n; k++) {
         part.assign(all.size() * ypileup::NCH + 1, 0); uint64_t st[5] = {0, 0, 0, 0, 0};
         int rc = ygpu_pileup_gather(feeders[k], all.data(), all.size(), part.data());
-        if (rc == 0) rc = ygpu_pileup_collect(feeders[k], nullptr, st);
+        if (rc == 0 && account) rc = ygpu_pileup_collect(feeders[k], nullptr, st);
         if (rc != 0) { err = ygpu_last_error(feeders[k]); *failed = k; return rc; }
         for (size_t w = 0; w < all.size() * ypileup::NCH; w++) rows[w] += part[w];
         devRecords += st[0]; devSkipped += st[1]; devDropped += st[2]; devHandedBack += st[3]; devCounted += st[4];
     }
     msGather = now() - t1;
+    return 0;
+}
+
+int PileupTrack::mergeDevices(ygpu_ctx *const *feeders, int n, const Genome &g, int *failed, std::string &err)
+{
+    const ydepth::Layout L = layout();
+    std::vector<uint32_t> all, rows;
+    const int rc = unionRows(feeders, n, true, true, g, all, rows, failed, err); if (rc != 0) return rc;
+    nCandidates = all.size();
     // ... and -pumin, with the routine the candidates were selected with
     sites.clear();
     for (size_t i = 0; i < all.size(); i++) {
@@ -123,6 +138,18 @@ int PileupTrack::mergeDevices(ygpu_ctx *const *feeders, int n, const Genome &g, 
         Site s; s.slot = all[i]; s.ref = code; memcpy(s.n, sum, sizeof s.n); sites.push_back(s);
     }
     return 0;
+}
+
+void PileupTrack::hostRows(std::vector<uint32_t> &slots, std::vector<uint32_t> &rows) const
+{
+    slots.clear(); rows.clear();
+    for (size_t b = 0; b < blocks.size(); b++) if (const uint32_t *blk = blocks[b]) {
+        const uint64_t s0 = (uint64_t)b * kBlock, s1 = std::min<uint64_t>(s0 + kBlock, nBins);
+        for (uint64_t s = s0; s < s1; s++) {
+            const uint32_t *r = blk + (size_t)(s - s0) * ypileup::NCH;
+            if (r[0] | r[1] | r[2] | r[3] | r[4] | r[5] | r[6]) { slots.push_back((uint32_t)s); rows.insert(rows.end(), r, r + ypileup::NCH); }
+        }
+    }
 }
 
 std::string PileupTrack::mergeNote() const

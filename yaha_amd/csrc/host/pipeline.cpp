@@ -28,16 +28,19 @@ namespace yaha {
 
 // ---- what a run writes ------------------------------------------------------------------------------------------------------------------------------------------
 // The side outputs the options ask for, in the order their files are written in and their keys stand in the stats line: the binned tracks (depth.cpp,
-// events.cpp, pileup.cpp), the breakpoint calls (junctions.cpp), the indel alleles (indels.cpp), the error profile (eprofile.cpp).  A new kind is one line here.
+// events.cpp, pileup.cpp), the breakpoint calls (junctions.cpp), the indel alleles (indels.cpp), the error profile (eprofile.cpp), the SNV calls (snv.cpp: they
+// judge the run's pileup -- the -opu track's if there is one, which has then written its table before them).  A new kind is one line here.
 static std::vector<std::unique_ptr<SideOutput>> makeSideOutputs(const Args &a)
 {
     std::vector<std::unique_ptr<SideOutput>> o;
     if (a.haveCov) o.emplace_back(new DepthTrack);
     if (a.haveEv) o.emplace_back(new EventsTrack);
-    if (a.havePu) o.emplace_back(new PileupTrack);
+    PileupTrack *pu = nullptr;
+    if (a.havePu) o.emplace_back(pu = new PileupTrack);
     if (a.haveBp) o.emplace_back(new JunctionTrack);
     if (a.haveId) o.emplace_back(new IndelTrack);
     if (a.haveEp) o.emplace_back(new EProfileTrack);
+    if (a.haveSnv) o.emplace_back(new SnvTrack(pu));
     return o;
 }
 // (the main output -- SAM / Blast8 text, BAM, sorted BAM -- is makeRecordSink's choice, bam.cpp)

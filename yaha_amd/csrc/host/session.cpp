@@ -87,6 +87,11 @@ int yaha_session_pileup_params(yaha_session *s, ygpu_pileup_params *p)
     if (sessionParams(s, p) != 0) return YGPU_EINVAL;
     p->min_mapq = (uint32_t)s->args.puMinQ; return 0;
 }
+int yaha_session_snv_params(yaha_session *s, ygpu_snv_params *p)
+{
+    if (!s || !p) return YGPU_EINVAL;
+    snvParamsFromArgs(s->args, *p); return 0;
+}
 int yaha_session_indel_params(yaha_session *s, ygpu_indel_params *p)
 {
     if (!s || !p) return YGPU_EINVAL;

@@ -91,12 +91,17 @@ struct Args {
     bool haveId = false, haveIdMin = false, haveIdLen = false, haveIdQ = false; std::string idFileName; int idMin = 2, idLen = 1, idMinQ = 0;
     // error profile: -oep FILE (substitution spectrum, indel lengths, identity of the records, errors by position in the read, of the printed records), -epq Q
     bool haveEp = false, haveEpQ = false; std::string epFileName; int epMinQ = 0;
+    // SNV calls: -osnv FILE (VCF 4.2: the sites the pileup genotypes as 0/1 or 1/1), -snverr E (sequencing error in per mille), -snvmin N (reads that carry the
+    // allele), -snvdp D (depth), -snvqual Q (QUAL in phred); the mapping-quality gate is the pileup's -puq
+    bool haveSnv = false, haveSnvErr = false, haveSnvMin = false, haveSnvDp = false, haveSnvQual = false; std::string snvFileName;
+    int snvErr = 100, snvMin = 2, snvDp = 4, snvQual = 20;
     bool query = false, index = true, compress = false, uncompress = false;   // -c / -u: .fa -> .nib2 / .nib2 -> .fasta only (Main.c:284-293, non-user builds of the reference)
 };
 void postProcessArgs(Args &a, bool query);                                  // AlignArgs.c:108-169
 // returns 0 to continue, >0 exit code+1 to stop (usage / error)
 int  parseArgs(int argc, char **argv, Args &a);                            // Main.c:187-565
 void paramsFromArgs(const Args &a, ygpu_params &p);
+void snvParamsFromArgs(const Args &a, ygpu_snv_params &p);                  // snv.cpp: the three costs from -snverr, the three thresholds
 std::string samHeader(const Args &a, const Genome &g);                      // AlignOutput.c:30-111
 
 // ---- reads (reference Query.c:63-228, QueryState.c:172-187) ---------------------------------------------
@@ -266,6 +271,7 @@ struct BinnedTrack : SideOutput {
     bool deviceEntryPoints() const { return haveEnable && devSize && devCollect; }      // does this build have the kind's ygpu_*_enable / _size / _collect?
     virtual int deviceEnable(ygpu_ctx *ctx) const = 0;                    // YGPU_ENODEV without the entry points
     int  deviceCollect(ygpu_ctx *ctx, std::string &err);                  // adds the image's array and statistics to this track
+    void feeders(std::vector<ygpu_ctx *> &ctx, std::vector<int> &dev) const;      // a feeding context per image that has one, image by image, with its HIP device
     // The end of the run: what the devices counted joins what the host counted.  feeders[k]: a context of index image k that fed the image's array (n may be 0).
     // Returns 0, or the device's error code with *failed = the image it came from.  Here: deviceCollect of every image; a kind whose array does not travel
     // (the pileup) has its own way.
@@ -318,6 +324,13 @@ struct PileupTrack : BinnedTrack {                                        // (a 
     void add(const OutClump &oc, const Read &r, Slot *) override;
     int  deviceEnable(ygpu_ctx *ctx) const override;
     int  mergeDevices(ygpu_ctx *const *feeders, int n, const Genome &g, int *failed, std::string &err) override;
+    // what mergeDevices stands on, for the SNV calls as well (snv.cpp): the sorted union of the sources' candidates -- the host's blocks if withHost, every
+    // feeder's selection -- and the sources' summed rows there (all.size() * 7 words); account: the feeders' statistics join this track's
+    int  unionRows(ygpu_ctx *const *feeders, int n, bool withHost, bool account, const Genome &g, std::vector<uint32_t> &all, std::vector<uint32_t> &rows, int *failed,
+                   std::string &err);
+    int  candidatesUnion(ygpu_ctx *const *feeders, int n, bool withHost, const Genome &g, std::vector<uint32_t> &all, int *failed, std::string &err);      // the union alone
+    // the host's counts as a list for ygpu_pileup_add: the slots of its blocks that hold something, ascending, and their rows
+    void hostRows(std::vector<uint32_t> &slots, std::vector<uint32_t> &rows) const;
     uint64_t sum() const override { return hostCounted + devCounted; }    // (the counts added: the sum over the arrays without reading 28 bytes a base)
     std::string extraStats() const override;
     std::string mergeNote() const override;
@@ -325,9 +338,9 @@ struct PileupTrack : BinnedTrack {                                        // (a 
   protected:
     bool allocate(std::string &err) override;                             // the table of blocks, all null (the bin must be 1)
     bool writeLines(FILE *f, const Genome &g) const override;
+    const uint32_t *row(uint32_t slot) const { const uint32_t *b = blocks[slot / kBlock]; return b ? b + (size_t)(slot % kBlock) * 7 : nullptr; }
   private:
     uint32_t *block(uint32_t slot);                                       // the block of a slot, made if it is not there yet
-    const uint32_t *row(uint32_t slot) const { const uint32_t *b = blocks[slot / kBlock]; return b ? b + (size_t)(slot % kBlock) * 7 : nullptr; }
 };
 
 // ---- split-read breakpoint calls (-obp; junctions.cpp, ../junction_core.h) ---------------------------------------------------------------------------------
@@ -421,6 +434,35 @@ struct EProfileTrack : SideOutput {
     bool write(const char *path, std::string &err) const;                 // path "stdout" = standard output
   private:
     const Genome *genome = nullptr; std::string file; std::vector<CtxAt> enabled;
+};
+
+// ---- SNV calls with genotypes (-osnv; snv.cpp, ../snv_core.h) ---------------------------------------------------------------------------------------------------
+// The seventh side output counts nothing itself: it judges the run's pileup -- the -opu track's when that option is given (`shared`: this kind's hooks then do
+// nothing, and the pileup's table has been written when finish runs), otherwise a PileupTrack of its own that writes no file and that every hook is handed on
+// to.  One device array per image, the host's blocks counted once.  finish folds every source into ONE image's array -- the first image with a feeder: the
+// host's blocks, then every other image's rows at the union of all sources' candidates (ygpu_pileup_add) --, selects the calls there (ygpu_snv_call_size /
+// ygpu_snv_collect) and writes the VCF.  A run over N images so moves roughly what -opu moves.  Without the entry points (the CPU tier's test doubles), without a
+// feeder, with YAHA_HOST_SNV=1 or when the selection fails before anything was folded, ysnv's routine runs on the host over the union of the sources
+// (PileupTrack::unionRows); when it fails after every fold was done, over the one image's candidates.  A fold that fails half-way leaves an array nobody can
+// read any more: the run fails.
+struct SnvTrack : SideOutput {
+    explicit SnvTrack(PileupTrack *sharedPileup) : shared(sharedPileup) {}
+    const char *name() const override { return "-osnv"; }
+    bool setup(const Args &a, const Genome &g, int nImages, int nContexts, std::string &err) override;
+    int  enable(const CtxAt &at) override { return own ? own->enable(at) : YGPU_ENODEV; }
+    int  beforeFilter(const CtxAt &at, size_t n) override { return own ? own->beforeFilter(at, n) : 0; }
+    void add(const OutClump &oc, const Read &r, Slot *s) override { if (own) own->add(oc, r, s); }
+    bool finish(FILE *mainOut, FILE *log, bool timing) override;
+    void stats(std::string &line) const override;
+    static bool deviceEntryPoints();                                      // does this build have ygpu_pileup_add and ygpu_snv_*?
+    std::vector<ygpu_snv_call> calls;                                     // what the writer prints, ascending (made by finish)
+    uint64_t nHet = 0, nHom = 0, foldedSlots = 0; bool onDevice = false;
+    bool write(const char *path, std::string &err) const;                 // path "stdout" = standard output
+  private:
+    int  callOnDevice(PileupTrack &pu, ygpu_ctx *const *feeders, int n, int *folded, std::string &err);      // *folded: 0 nothing, 1 every source, 2 half-way
+    int  callOnHost(PileupTrack &pu, ygpu_ctx *const *feeders, int n, bool withHost, std::string &err);
+    PileupTrack *shared; std::unique_ptr<PileupTrack> own; const Genome *genome = nullptr; std::string file, options; ygpu_snv_params P{};
+    double msFold = 0, msSelect = 0, msWrite = 0;
 };
 
 // ---- the main output of a query run: where the formatted records of the batches go (sam.cpp: SAM / Blast8 text; bam.cpp: BAM, sorted BAM) -----------------
