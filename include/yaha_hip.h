@@ -468,6 +468,11 @@ typedef struct ygpu_fragment {
 /* A1+A2 for the resident batch: fragments sorted by (read, strand, diag, SQO). Output owned by ctx. */
 int  ygpu_seed_join(ygpu_ctx *ctx, const ygpu_fragment **frags, uint64_t *n_frags);
 
+/* The same, but the fragment array as ygpu_run builds it: a fragment of ONE hit whose neighbouring fragments of its
+ * (read, strand) are both more than maxGap diagonals away is not written (it cannot become a clump while
+ * wordLen < minMatch; with wordLen >= minMatch every fragment is kept).  refLen is set.  Output owned by ctx. */
+int  ygpu_seed_join_kept(ygpu_ctx *ctx, const ygpu_fragment **frags, uint64_t *n_frags);
+
 /* A3+A4 on the fragments of the last ygpu_seed_join: per clump (in creation order per read/strand) the
  * ordered fragment list before alignClump. clump_frag_start has n_clumps+1 entries. */
 int  ygpu_chain(ygpu_ctx *ctx, const ygpu_fragment **clump_frags, const uint32_t **clump_frag_start,

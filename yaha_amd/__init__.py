@@ -189,7 +189,7 @@ EXPORTS = (
     "ygpu_junctions_enable", "ygpu_junctions_size", "ygpu_junctions_collect", "yaha_session_junction_params",
     "ygpu_bgzf_open", "ygpu_bgzf_bound", "ygpu_bgzf_compress", "ygpu_bgzf_last_error", "ygpu_bgzf_close",
     "ygpu_bamsort_open", "ygpu_bamsort_append", "ygpu_bamsort_sort", "ygpu_bamsort_next", "ygpu_bamsort_info", "ygpu_bamsort_last_error", "ygpu_bamsort_close",
-    "ygpu_submit", "ygpu_poll", "ygpu_wait", "ygpu_seed_join", "ygpu_chain", "ygpu_dp_batch", "ygpu_dp_batch_ex",
+    "ygpu_submit", "ygpu_poll", "ygpu_wait", "ygpu_seed_join", "ygpu_seed_join_kept", "ygpu_chain", "ygpu_dp_batch", "ygpu_dp_batch_ex",
     "yaha_session_open", "yaha_session_close", "yaha_session_error", "yaha_session_params",
     "yaha_session_index_view", "yaha_session_header", "yaha_session_next_batch", "yaha_session_emit", "yaha_session_postfilter_params", "yaha_session_emit_filtered",
     "yaha_build_index", "yaha_main")
@@ -545,9 +545,12 @@ class Context:
         self._check(lib().ygpu_last_timing(self._h, C.byref(tot), C.byref(n), C.byref(names), C.byref(ms)), "ygpu_last_timing")
         return tot.value, {names[i].decode(): ms[i] for i in range(n.value)}
 
-    def seed_join(self):
+    def seed_join(self, kept=False):
+        """The fragments of the uploaded batch (ygpu_seed_join): every one, or with kept=True the array as run() builds it, without the single-hit fragments
+        that have no neighbour within maxGap diagonals (ygpu_seed_join_kept)."""
         f, n = C.POINTER(Fragment)(), C.c_uint64()
-        self._check(lib().ygpu_seed_join(self._h, C.byref(f), C.byref(n)), "ygpu_seed_join")
+        call = lib().ygpu_seed_join_kept if kept else lib().ygpu_seed_join
+        self._check(call(self._h, C.byref(f), C.byref(n)), call.__name__)
         return f, n.value
 
     def chain(self):

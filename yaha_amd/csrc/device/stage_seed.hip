@@ -159,7 +159,7 @@ int stageSeed(ygpu_ctx *ctx)
     EV1(T_SORT);
     return 0;
 }
-// The workgroup sort against std::stable_sort on the host, both rankings, four shapes: segments of every fill (one hit, a partial last row, full), diagonals that are
+// The workgroup sort against std::stable_sort on the host, both rankings, every shape: segments of every fill (one hit, a partial last row, full), diagonals that are
 // random, all equal, two values alternating lane by lane, equal inside a row and in runs across rows (what the lane order of the LDS atomics has to get right),
 // query offsets ascending in input order.  (ygpu_selftest_primitives)
 template <unsigned BS, unsigned IPT>
@@ -221,11 +221,14 @@ static int selftestSegSortShape(ygpu_ctx *ctx, uint64_t &x, char *why, size_t wh
 int ydSelftestSegSort(ygpu_ctx *ctx, uint64_t &x)
 {
     static thread_local char why[256]; int rc;
-    rc = selftestSegSortShape<128, 8>(ctx, x, why, sizeof why); if (rc) return rc;
-    rc = selftestSegSortShape<256, 16>(ctx, x, why, sizeof why); if (rc) return rc;
-    rc = selftestSegSortShape<512, 20>(ctx, x, why, sizeof why); if (rc) return rc;
-    rc = selftestSegSortShape<512, YD_SORT_TOP>(ctx, x, why, sizeof why); if (rc) return rc;
-    return selftestSegSortShape<1024, 16>(ctx, x, why, sizeof why);
+    // every shape stageSeed launches (YD_SORT_CLASS), the YGPU_SORT_WIDE=0 ones included: a wrong shape is named by shape
+#define YD_SELFTEST_SHAPE(BS, IPT) rc = selftestSegSortShape<BS, IPT>(ctx, x, why, sizeof why); if (rc) return rc
+    YD_SELFTEST_SHAPE(128, 8); YD_SELFTEST_SHAPE(128, 16); YD_SELFTEST_SHAPE(256, 12); YD_SELFTEST_SHAPE(256, 16);
+    YD_SELFTEST_SHAPE(512, 10); YD_SELFTEST_SHAPE(512, 12); YD_SELFTEST_SHAPE(512, 14); YD_SELFTEST_SHAPE(512, 16);
+    YD_SELFTEST_SHAPE(512, 20); YD_SELFTEST_SHAPE(512, 24); YD_SELFTEST_SHAPE(512, 28); YD_SELFTEST_SHAPE(512, YD_SORT_TOP);
+    YD_SELFTEST_SHAPE(1024, 10); YD_SELFTEST_SHAPE(1024, 12); YD_SELFTEST_SHAPE(1024, 14); YD_SELFTEST_SHAPE(1024, 16);
+#undef YD_SELFTEST_SHAPE
+    return 0;
 }
 
 // (Re)creates the fragment array from the sorted keys -- the chain stage trims it in place, so a redo of that stage comes back here.  One kernel (seed.h:
@@ -320,13 +323,18 @@ int ygpu_upload(ygpu_ctx *ctx, const ygpu_read_batch *b) { return uploadBatch(ct
 /* ygpu_upload without its wait: returns as soon as the copies are queued.  The batch's memory must stay unchanged until the ygpu_run that follows has returned. */
 int ygpu_upload_nowait(ygpu_ctx *ctx, const ygpu_read_batch *b) { static const bool waitAnyway = getenv("YGPU_UPLOAD_WAIT") != nullptr; return uploadBatch(ctx, b, waitAnyway); }
 
-int ygpu_seed_join(ygpu_ctx *ctx, const ygpu_fragment **frags, uint64_t *n_frags)
+// stage 1 of the resident batch and its fragment array on the host; keepAll: every fragment (ygpu_seed_join), else the array as ygpu_run builds it -- the dead
+// singles of seed.h dropped -- with refLen finished here (k_frag_finish: the run leaves that to k_region_scan)
+static int seedJoinTo(ygpu_ctx *ctx, bool keepAll, const ygpu_fragment **frags, uint64_t *n_frags)
 {
     if (!ctx || !ctx->stream) return YGPU_EINVAL;
-    ctx->stageDone = 0; ctx->keepAllFrags = true; int rc = runTo(ctx, 1); ctx->keepAllFrags = false; if (rc) return rc;
+    ctx->stageDone = 0; ctx->keepAllFrags = keepAll; int rc = runTo(ctx, 1); ctx->keepAllFrags = false; if (rc) return rc;
+    if (!keepAll && ctx->nFrags) KL(k_frag_finish, dim3(gridFor(ctx->nFrags, 256)), dim3(256), 0, ctx->stream, ctx->frags.as<DevFrag>(), ctx->nFrags);
     ctx->hFrags.resize(ctx->nFrags);
     if (ctx->nFrags) HIPCHK(hipMemcpy(ctx->hFrags.data(), ctx->frags.p, 16ull * ctx->nFrags, hipMemcpyDeviceToHost));
     for (auto &f : ctx->hFrags) f.reserved = 0;
     *frags = ctx->hFrags.data(); *n_frags = ctx->nFrags; return 0;
 }
+int ygpu_seed_join(ygpu_ctx *ctx, const ygpu_fragment **frags, uint64_t *n_frags) { return seedJoinTo(ctx, true, frags, n_frags); }
+int ygpu_seed_join_kept(ygpu_ctx *ctx, const ygpu_fragment **frags, uint64_t *n_frags) { return seedJoinTo(ctx, false, frags, n_frags); }
 }  // extern "C"
