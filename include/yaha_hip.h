@@ -361,6 +361,39 @@ int  ygpu_indels_enable(ygpu_ctx *ctx, const ygpu_indel_params *p);            /
 int  ygpu_indels_size(ygpu_ctx *ctx, uint64_t *used);
 int  ygpu_indels_collect(ygpu_ctx *ctx, ygpu_indel_entry *out, uint64_t stats[6]);
 
+/* ---- indel calls with genotypes: the raw alleles left-normalised, merged and judged at their anchor base (optional; needs ygpu_pileup_enable) -----------------
+ * The step behind the indel alleles and the pileup: a raw allele sits where the aligner happened to put the gap, so one indel of a homopolymer or tandem repeat
+ * can be spread over several keys.  The contract (yaha_amd/csrc/indelcall_core.h -- one set of routines for host and device): p = the key's slot, the anchor is
+ * p - 1; an insertion of more than 42 bases and an allele at the first slot of its sequence are `skipped` (so are keys that are no event of the layout: a slot
+ * past it, length 0, a deletion past the end of its sequence); the shift s is the first i < min(max_shift, p - 1 - first slot of the sequence) at which
+ * ref[p-1-i] differs from ref[p+L-1-i] (deletion) or from I[L-1-(i mod L)] (insertion), or either is not one of A C G T; the normalised allele has slot p - s
+ * and, an insertion, its bases rotated right by s mod L; equal normalised keys are ONE allele whose counts add, saturated at 2^32 - 1.  An allele is judged with
+ * d = A + C + G + T + N + DEL of the pileup row at its anchor, a = its count, r = max(d - a, 0): PL0 = r cost_match + a cost_error, PL1 = (r + a) cost_het,
+ * PL2 = r cost_error + a cost_match, GT / QUAL / GQ as for the SNV calls; a call needs GT != 0, a >= min_alt, d >= min_depth, QUAL >= min_qual.
+ * ygpu_indelcall_normalize takes the run's raw alleles (host memory; counted with min_length 1 and the pileup's gate), normalises them on the device -- a wave per
+ * allele reads the image's reference 64 bases a step, the first mismatch comes from one ballot -- and merges them in a table of the context's own (compare-and-
+ * swap on the key's words, a 64-bit atomic add of the count: sums of integers, the same whatever order the atomics are served in).  *n_out = merged alleles;
+ * stats (may be NULL) = raw alleles, alleles that moved, alleles merged away, alleles skipped.  The layout is the pileup's: ygpu_pileup_enable first.
+ * ygpu_indelcall_alleles copies the merged alleles of the last normalize, ygpu_indelcall_size judges every one of them against the image's pileup array AS IT
+ * STANDS (fold the other sources with ygpu_pileup_add first) and returns the number of calls, ygpu_indelcall_collect copies the records of the last selection.
+ * Both lists leave in the order of indel_core.h's keyLess: the table keeps no order, so the records selected on the device -- the calls alone -- are put into it
+ * by the host side of the call.  A second ygpu_indelcall_size, with other parameters, selects again.  Like the SNV calls these wait for everything queued on the
+ * device, use the post-filter's side of the context and serve a parked context. */
+typedef struct ygpu_indelcall_params {
+    uint32_t cost_match, cost_error, cost_het;          /* 1/100 phred: a read that agrees with the genotype / disagrees / one of a heterozygote's two */
+    uint32_t min_alt, min_depth, min_qual;              /* reads that carry the allele, reads that cover the anchor, whole phred */
+    uint32_t reserved[2];                               /* zero */
+} ygpu_indelcall_params;
+/* 64 bytes.  w0 .. w2: the normalised key (indel_core.h); info = GT | the 4-bit reference code of the anchor << 4; counts and PLs saturate at 2^32 - 1 */
+typedef struct ygpu_indel_call {
+    uint64_t w0, w1, w2;
+    uint32_t alt_count, ref_count, depth, qual, gq, pl[3], info, zero;
+} ygpu_indel_call;
+int  ygpu_indelcall_normalize(ygpu_ctx *ctx, const ygpu_indel_entry *raw, uint64_t n, uint32_t max_shift, uint64_t *n_out, uint64_t stats[4]);
+int  ygpu_indelcall_alleles(ygpu_ctx *ctx, ygpu_indel_entry *out);                                  /* out[n_out] of the last normalize, keyLess order */
+int  ygpu_indelcall_size(ygpu_ctx *ctx, const ygpu_indelcall_params *p, uint64_t *n);              /* selects; *n = calls over the array as it stands */
+int  ygpu_indelcall_collect(ygpu_ctx *ctx, ygpu_indel_call *calls);                                 /* calls[n] of the last ygpu_indelcall_size, keyLess order */
+
 /* ---- the error profile: how good the printed alignments are (optional, behind ygpu_postfilter) -----------------------------------------------------------------
  * What the other outputs leave out: the substitution spectrum, the lengths of insertions and deletions, the identity the records reach and the error rate
  * along the read.  With ygpu_eprofile_enable, every ygpu_postfilter of the context also adds the clumps it returns to ONE table of YGPU_EPROFILE_WORDS = 1556
@@ -536,6 +569,8 @@ int  yaha_session_events_params(yaha_session *s, ygpu_events_params *p);
 int  yaha_session_pileup_params(yaha_session *s, ygpu_pileup_params *p);
 /* For ygpu_snv_call_size: the three costs derived from -snverr (default 100 per mille), -snvmin (2), -snvdp (4) and -snvqual (20). */
 int  yaha_session_snv_params(yaha_session *s, ygpu_snv_params *p);
+/* For ygpu_indelcall_size: the three costs derived from -inderr (default 50 per mille: 22, 1301, 301), -indmin (2), -inddp (4) and -indqual (20). */
+int  yaha_session_indelcall_params(yaha_session *s, ygpu_indelcall_params *p);
 /* The same for ygpu_indels_enable: -idq (default 0), -idlen (default 1), capacity 0 and the sequence table (pointers of their own into the session). */
 int  yaha_session_indel_params(yaha_session *s, ygpu_indel_params *p);
 /* The same for ygpu_eprofile_enable: -epq (default 0) and the sequence table (pointers of their own into the session). */

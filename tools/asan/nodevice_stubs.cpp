@@ -47,6 +47,10 @@ int  ygpu_snv_collect(ygpu_ctx *, ygpu_snv_call *) { return YGPU_ENODEV; }
 int  ygpu_indels_enable(ygpu_ctx *, const ygpu_indel_params *) { return YGPU_ENODEV; }
 int  ygpu_indels_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
 int  ygpu_indels_collect(ygpu_ctx *, ygpu_indel_entry *, uint64_t *) { return YGPU_ENODEV; }
+int  ygpu_indelcall_normalize(ygpu_ctx *, const ygpu_indel_entry *, uint64_t, uint32_t, uint64_t *, uint64_t *) { return YGPU_ENODEV; }
+int  ygpu_indelcall_alleles(ygpu_ctx *, ygpu_indel_entry *) { return YGPU_ENODEV; }
+int  ygpu_indelcall_size(ygpu_ctx *, const ygpu_indelcall_params *, uint64_t *) { return YGPU_ENODEV; }
+int  ygpu_indelcall_collect(ygpu_ctx *, ygpu_indel_call *) { return YGPU_ENODEV; }
 int  ygpu_eprofile_enable(ygpu_ctx *, const ygpu_eprofile_params *) { return YGPU_ENODEV; }
 int  ygpu_eprofile_size(ygpu_ctx *, uint64_t *) { return YGPU_ENODEV; }
 int  ygpu_eprofile_collect(ygpu_ctx *, uint64_t *, uint64_t *) { return YGPU_ENODEV; }

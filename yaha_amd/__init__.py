@@ -136,6 +136,17 @@ class IndelEntry(C.Structure):
         return "".join("ACGTN"[min(4, ((self.w1 >> (3 * i)) if i < 21 else (self.w2 >> (3 * (i - 21)))) & 7)] for i in range(n))
 
 
+class IndelCallParams(C.Structure):
+    """The three costs in 1/100 phred and the three thresholds of an indel call (include/yaha_hip.h: ygpu_indelcall_params)."""
+    _fields_ = [("cost_match", C.c_uint32), ("cost_error", C.c_uint32), ("cost_het", C.c_uint32), ("min_alt", C.c_uint32), ("min_depth", C.c_uint32),
+                ("min_qual", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+# one call (ygpu_indel_call, 64 bytes): the normalised key's three words (uint64), then uint32 words; info = GT | the anchor's 4-bit reference code << 4
+INDEL_CALL_FIELDS = ("w0", "w1", "w2", "alt_count", "ref_count", "depth", "qual", "gq", "pl0", "pl1", "pl2", "info", "zero")
+INDEL_CALL_STATS = ("raw", "shifted", "merged", "skipped")
+
+
 INDEL_STATS = ("records_counted", "records_skipped_mapq", "records_dropped_two_sequences", "events", "reads_left_to_host", "events_lost")
 
 
@@ -185,6 +196,7 @@ EXPORTS = (
     "yaha_session_pileup_params",
     "ygpu_pileup_add", "ygpu_snv_call_size", "ygpu_snv_collect", "yaha_session_snv_params",
     "ygpu_indels_enable", "ygpu_indels_size", "ygpu_indels_collect", "yaha_session_indel_params",
+    "ygpu_indelcall_normalize", "ygpu_indelcall_alleles", "ygpu_indelcall_size", "ygpu_indelcall_collect", "yaha_session_indelcall_params",
     "ygpu_eprofile_enable", "ygpu_eprofile_size", "ygpu_eprofile_collect", "yaha_session_eprofile_params",
     "ygpu_junctions_enable", "ygpu_junctions_size", "ygpu_junctions_collect", "yaha_session_junction_params",
     "ygpu_bgzf_open", "ygpu_bgzf_bound", "ygpu_bgzf_compress", "ygpu_bgzf_last_error", "ygpu_bgzf_close",
@@ -482,6 +494,39 @@ class Context:
         table is empty afterwards (ygpu_indels_collect)."""
         out, n, st = self._collect(lib().ygpu_indels_size, lib().ygpu_indels_collect, lambda n: ((IndelEntry * max(1, n))(),) * 2, INDEL_STATS)
         return [out[i] for i in range(n)], st
+
+    def indelcall_normalize(self, entries, max_shift=256):
+        """Left-normalises and merges raw indel alleles on the device (ygpu_indelcall_normalize; after pileup_enable(), whose layout it uses).  entries: IndelEntry
+        objects or (w0, w1, w2, count) tuples.  Returns (merged alleles, the statistics as a dict with the keys INDEL_CALL_STATS)."""
+        n = len(entries); arr = (IndelEntry * max(1, n))()
+        for i, e in enumerate(entries):
+            w0, w1, w2, cnt = (e.w0, e.w1, e.w2, e.count) if isinstance(e, IndelEntry) else e
+            arr[i].w0, arr[i].w1, arr[i].w2, arr[i].count, arr[i].zero = w0, w1, w2, cnt, 0
+        n_out = C.c_uint64(); st = (C.c_uint64 * 4)()
+        self._check(lib().ygpu_indelcall_normalize(self._h, arr, C.c_uint64(n), C.c_uint32(max_shift), C.byref(n_out), st), "ygpu_indelcall_normalize")
+        self._ic_n = int(n_out.value)
+        return self._ic_n, dict(zip(INDEL_CALL_STATS, (int(x) for x in st)))
+
+    def indelcall_alleles(self):
+        """The merged, normalised alleles of the last indelcall_normalize() in the order of the file (ygpu_indelcall_alleles): a list of IndelEntry."""
+        n = getattr(self, "_ic_n", 0); out = (IndelEntry * max(1, n))()
+        self._check(lib().ygpu_indelcall_alleles(self._h, out), "ygpu_indelcall_alleles")
+        return [out[i] for i in range(n)]
+
+    def indel_calls(self, session_or_params):
+        """The calls among the merged alleles, judged on the device against the image's pileup array as it stands (ygpu_indelcall_size / ygpu_indelcall_collect): a
+        structured numpy array with the fields INDEL_CALL_FIELDS (three uint64, then uint32).  The parameters: an IndelCallParams, or a Session."""
+        import numpy as np
+        p = session_or_params
+        if not isinstance(p, IndelCallParams):
+            p = IndelCallParams()
+            if lib().yaha_session_indelcall_params(session_or_params._h, C.byref(p)) != 0:
+                raise RuntimeError("yaha_session_indelcall_params: " + lib().yaha_session_error(session_or_params._h).decode())
+        n = C.c_uint64()
+        self._check(lib().ygpu_indelcall_size(self._h, C.byref(p), C.byref(n)), "ygpu_indelcall_size")
+        out = np.zeros(max(1, n.value), dtype=np.dtype([(f, np.uint64 if f in ("w0", "w1", "w2") else np.uint32) for f in INDEL_CALL_FIELDS]))
+        self._check(lib().ygpu_indelcall_collect(self._h, out.ctypes.data_as(C.c_void_p)), "ygpu_indelcall_collect")
+        return out[:n.value]
 
     def eprofile_enable(self, session):
         """The error profile of the printed clumps behind postfilter() (ygpu_eprofile_enable), in a table of this context's own, with the session's -epq and

@@ -364,7 +364,7 @@ std::vector<DevBuf *> allBuffers(ygpu_ctx *ctx)
                              &ctx->oqThr, &ctx->oqSeqStart, &ctx->oqSeqLen, &ctx->oqNeed, &ctx->oqPoolOff, &ctx->oqKeys, &ctx->oqStack, &ctx->oqNodes, &ctx->oqPrim, &ctx->oqPA,
                              &ctx->oqPfx, &ctx->oqPath, &ctx->oqPool, &ctx->oqPush, &ctx->oqOut, &ctx->oqOutCnt, &ctx->oqOutOps, &ctx->oqPrimCnt, &ctx->oqOutStart,
                              &ctx->oqOpsStart, &ctx->oqFClumps, &ctx->oqFOps, &ctx->jnCnt, &ctx->jnStart, &ctx->jnOut, &ctx->jnStats, &ctx->jnSeqStart, &ctx->jnSeqLen,
-                         &ctx->epTable, &ctx->epSeqs, &ctx->snvOut,
+                         &ctx->epTable, &ctx->epSeqs, &ctx->snvOut, &ctx->icRaw, &ctx->icTable, &ctx->icStats, &ctx->icAlleles, &ctx->icOut,
                          &ctx->puFwd, &ctx->puReadOff, &ctx->puTileCnt, &ctx->puTileStart, &ctx->puCand, &ctx->puSlots, &ctx->puRows,
                          &ctx->idTable, &ctx->idStats, &ctx->idSeqStart, &ctx->idSeqLen, &ctx->idBinBase, &ctx->idTileCnt, &ctx->idTileStart, &ctx->idOut};
     return std::vector<DevBuf *>(all, all + sizeof all / sizeof all[0]);

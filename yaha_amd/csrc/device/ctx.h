@@ -216,6 +216,11 @@ struct ygpu_ctx {
     // candidates' buffers, a fold's list and rows the gather's)
     DevBuf snvOut;
     uint64_t snvN = 0; bool snvHave = false;
+    // indel calls (-oindel; indelcall_stage.h, ../indelcall_core.h): the caller's raw alleles, the merge table of the last normalize (icCap entries, a power of
+    // two) with its statistics (three 64-bit words, then the used word), the merged alleles drained from it (the tiles' counts and sums are the indel table's
+    // buffers), and the records of the last selection over them
+    DevBuf icRaw, icTable, icStats, icAlleles, icOut;
+    uint64_t icCap = 0, icN = 0, icCalls = 0; bool icHave = false, icHaveCalls = false;
     // indel alleles (-oid; indel_stage.h, ../indel_core.h): the context's own hash table (idCap entries of 32 bytes, a power of two; idAuto: sized by the rule and
     // made larger, while empty, before a larger batch), its statistics (eight 64-bit words, then the used and the lost word), the sequence table and slot bases
     // of its layout, and for draining the occupied entries per tile, their exclusive sums and the compacted entries.  The stage reads the bases from puFwd /

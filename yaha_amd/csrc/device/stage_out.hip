@@ -4,7 +4,8 @@
 // (events_stage.h), and when ygpu_pileup_enable did, their allele pileup (pileup_stage.h: the one track that reads the reads' bases, which the snapshot then copies
 // as well), and when ygpu_indels_enable did, their indel alleles in the context's own hash table (indel_stage.h); and when ygpu_junctions_enable did, the
 // batch's split-read junctions (junction_stage.h), which leave with the filtered batch; and when ygpu_eprofile_enable did, their error profile in the context's
-// own table of counters (eprofile_stage.h).  At the end of a run the pileup array also gives the SNV calls (snv_stage.h: folds into it, the selection over it).
+// own table of counters (eprofile_stage.h).  At the end of a run the pileup array also gives the SNV calls (snv_stage.h: folds into it, the selection over it) and,
+// with the run's raw indel alleles, the indel calls (indelcall_stage.h: the left shift, the merge, the selection at the anchors).
 #include "ctx.h"
 #include "oqc_stage.h"
 #include "depth_stage.h"
@@ -12,8 +13,10 @@
 #include "pileup_stage.h"
 #include "snv_stage.h"
 #include "indel_stage.h"
+#include "indelcall_stage.h"
 #include "eprofile_stage.h"
 #include "junction_stage.h"
+#include <algorithm>
 #include <map>
 #include <tuple>
 
@@ -632,6 +635,130 @@ int ygpu_indels_collect(ygpu_ctx *full, ygpu_indel_entry *out, uint64_t stats[6]
     tlsPfFailed = nullptr;
     full->idUsed = 0;
     if (stats) { for (int k = 0; k < 5; k++) stats[k] = h[k]; stats[5] = (uint32_t)(h[8] >> 32); }
+    return 0;
+}
+// ---- indel calls (indelcall_stage.h; the contract is in ../indelcall_core.h) --------------------------------------------------------------------------------------
+// The raw alleles normalised against the image's reference and merged in a table of the context's own, made (and cleared) for the call; the layout is the
+// pileup's.  On the post-filter's side of the context, once everything queued on the device has finished; serves a parked context as the SNV calls do.
+static bool indelEntryLess(const ygpu_indel_entry &a, const ygpu_indel_entry &b)
+{
+    return yindel::keyLess(yindel::Key{a.w0, a.w1, a.w2}, yindel::Key{b.w0, b.w1, b.w2});
+}
+int ygpu_indelcall_normalize(ygpu_ctx *full, const ygpu_indel_entry *raw, uint64_t n, uint32_t max_shift, uint64_t *n_out, uint64_t stats[4])
+{
+    if (!full || !full->stream || !n_out || (n && !raw)) return YGPU_EINVAL;
+    if (!full->track[TRACK_PILEUP]) { full->err = "ygpu_indelcall_normalize: ygpu_pileup_enable has not been called on this context (the layout is the pileup's)";
+        return YGPU_EINVAL; }
+    if (max_shift > (uint32_t)yindelcall::MAX_SHIFT || n > (1ull << 30)) { full->err = "ygpu_indelcall_normalize: max_shift must be at most 65535, n at most 2^30";
+        return YGPU_EINVAL; }
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    HIPCHK(hipDeviceSynchronize());
+    const TrackImage &T = *full->track[TRACK_PILEUP];
+    full->icHave = full->icHaveCalls = false; full->icN = full->icCalls = 0;
+    if (stats) { stats[0] = n; stats[1] = stats[2] = stats[3] = 0; }
+    *n_out = 0;
+    if (n == 0) { tlsPfFailed = nullptr; full->icHave = true; return 0; }
+    int rc = pileupSide(full); if (rc) return rc;
+    uint64_t capacity = 1024; while (capacity < 2 * n) capacity <<= 1;
+    ENSURE(full->icRaw, sizeof(ygpu_indel_entry) * n); ENSURE(full->icTable, sizeof(ygpu_indel_entry) * capacity); ENSURE(full->icStats, 64);
+    full->icCap = capacity;
+    HIPCHK(hipMemcpyAsync(full->icRaw.p, raw, sizeof(ygpu_indel_entry) * n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(full->icTable.p, 0, sizeof(ygpu_indel_entry) * capacity, ctx->stream));
+    HIPCHK(hipMemsetAsync(full->icStats.p, 0, 64, ctx->stream));
+    IndelNormArgs N; N.L = trackLayout(T); N.nSlots = T.nBins; N.bases = full->dBases.as<uint8_t>(); N.nBaseBytes = full->dBases.cap;
+    N.raw = full->icRaw.as<ygpu_indel_entry>(); N.n = (uint32_t)n; N.maxShift = max_shift; N.table = full->icTable.as<ygpu_indel_entry>(); N.mask = (uint32_t)(capacity - 1);
+    N.stats = full->icStats.as<unsigned long long>(); N.used = full->icStats.as<uint32_t>() + 8;
+    KL(k_indel_norm, dim3(gridFor(n * 64, 256)), dim3(256), 0, ctx->stream, N);
+    // the table's occupied entries, compacted: the indel table's count and sums, the emit that saturates
+    const uint32_t nTiles = (uint32_t)((capacity + YI_TILE - 1) / YI_TILE);
+    ENSURE(full->idTileCnt, 4ull * (nTiles + 2)); ENSURE(full->idTileStart, 4ull * (nTiles + 2));
+    HIPCHK(hipMemsetAsync((uint32_t *)full->idTileCnt.p + nTiles, 0, 8, ctx->stream));
+    IndelDrainArgs A; A.table = full->icTable.as<ygpu_indel_entry>(); A.capacity = capacity; A.nTiles = nTiles; A.cnt = full->idTileCnt.as<uint32_t>();
+    A.start = full->idTileStart.as<uint32_t>(); A.out = nullptr; A.cap = 0;
+    const dim3 grid(gridFor((uint64_t)nTiles * 64, 256));
+    KL(k_indel_count, grid, dim3(256), 0, ctx->stream, A);
+    rc = cubScan(ctx, full->idTileCnt.as<uint32_t>(), full->idTileStart.as<uint32_t>(), nTiles + 1); if (rc) return rc;
+    uint32_t tot = 0, scanFail = 0; unsigned long long h[4] = {0, 0, 0, 0};
+    { const FetchPiece pc[3] = {{full->idTileStart.as<uint32_t>() + nTiles, &tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1},
+        {full->icStats.p, (uint32_t *)h, 8}}; rc = fetchMany(ctx, pc, 3); if (rc) return rc; }
+    if (scanFail) return scanGaveUp(ctx, "indel calls");
+    if (h[2]) { ctx->err = "ygpu_indelcall_normalize: a normalised allele found no entry in the merge table"; return YGPU_EINTERNAL; }
+    if (tot) {
+        ENSURE(full->icAlleles, sizeof(ygpu_indel_entry) * (uint64_t)tot);
+        A.out = full->icAlleles.as<ygpu_indel_entry>(); A.cap = tot;
+        KL(k_indelcall_drain, grid, dim3(256), 0, ctx->stream, A);
+    }
+    HIPCHK(streamSync(ctx));
+    tlsPfFailed = nullptr;
+    full->icN = tot; full->icHave = true; *n_out = tot;
+    if (stats) { stats[1] = h[0]; stats[3] = h[1]; stats[2] = n - h[1] - tot; }
+    return 0;
+}
+int ygpu_indelcall_alleles(ygpu_ctx *full, ygpu_indel_entry *out)
+{
+    if (!full || !full->stream) return YGPU_EINVAL;
+    if (!full->icHave) { full->err = "ygpu_indelcall_alleles: ygpu_indelcall_normalize has not been called on this context"; return YGPU_EINVAL; }
+    if (!full->icN) return 0;
+    if (!out || !full->icAlleles.p) return YGPU_EINVAL;
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    HIPCHK(hipMemcpyAsync(out, full->icAlleles.p, sizeof(ygpu_indel_entry) * full->icN, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
+    tlsPfFailed = nullptr;
+    std::sort(out, out + full->icN, indelEntryLess);                           // (the table keeps no order: see the header)
+    return 0;
+}
+// The calls among the merged alleles against the image's array as it stands: count a tile, exclusive sums, emit -- the SNV calls' three steps, a lane an allele.
+int ygpu_indelcall_size(ygpu_ctx *full, const ygpu_indelcall_params *p, uint64_t *n)
+{
+    if (!full || !full->stream || !p || !n) return YGPU_EINVAL;
+    if (!full->track[TRACK_PILEUP]) { full->err = "ygpu_indelcall_size: ygpu_pileup_enable has not been called on this context"; return YGPU_EINVAL; }
+    if (!full->icHave) { full->err = "ygpu_indelcall_size: ygpu_indelcall_normalize has not been called on this context"; return YGPU_EINVAL; }
+    if (p->min_alt < 1 || p->min_depth < 1) { full->err = "ygpu_indelcall_size: min_alt and min_depth must be at least 1"; return YGPU_EINVAL; }
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    HIPCHK(hipDeviceSynchronize());
+    full->icHaveCalls = false; full->icCalls = 0; *n = 0;
+    if (!full->icN || !full->icAlleles.p) { tlsPfFailed = nullptr; full->icHaveCalls = true; return 0; }
+    const TrackImage &T = *full->track[TRACK_PILEUP];
+    int rc = pileupSide(full); if (rc) return rc;
+    const uint32_t nAl = (uint32_t)full->icN, nTiles = (nAl + YC_TILE - 1) / YC_TILE;
+    ENSURE(full->idTileCnt, 4ull * (nTiles + 2)); ENSURE(full->idTileStart, 4ull * (nTiles + 2));
+    HIPCHK(hipMemsetAsync((uint32_t *)full->idTileCnt.p + nTiles, 0, 8, ctx->stream));
+    IndelCallArgs A; A.L = trackLayout(T); A.pu = T.data.as<uint32_t>(); A.nSlots = (uint32_t)T.nBins; A.bases = full->dBases.as<uint8_t>(); A.nBaseBytes = full->dBases.cap;
+    A.alleles = full->icAlleles.as<ygpu_indel_entry>(); A.n = nAl; A.nTiles = nTiles; A.P = *p;
+    A.cnt = full->idTileCnt.as<uint32_t>(); A.start = full->idTileStart.as<uint32_t>(); A.out = nullptr; A.cap = 0;
+    const dim3 grid(gridFor((uint64_t)nTiles * 64, 256));
+    KL(k_indelcall_count, grid, dim3(256), 0, ctx->stream, A);
+    rc = cubScan(ctx, full->idTileCnt.as<uint32_t>(), full->idTileStart.as<uint32_t>(), nTiles + 1); if (rc) return rc;
+    uint32_t tot = 0, scanFail = 0;
+    { const FetchPiece pc[2] = {{full->idTileStart.as<uint32_t>() + nTiles, &tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1}};
+      rc = fetchMany(ctx, pc, 2); if (rc) return rc; }
+    if (scanFail) return scanGaveUp(ctx, "indel calls");
+    ENSURE(full->icOut, sizeof(ygpu_indel_call) * ((uint64_t)tot + 1));
+    A.out = full->icOut.as<ygpu_indel_call>(); A.cap = tot;
+    if (tot) KL(k_indelcall_emit, grid, dim3(256), 0, ctx->stream, A);
+    HIPCHK(streamSync(ctx));
+    tlsPfFailed = nullptr;
+    full->icCalls = tot; full->icHaveCalls = true; *n = tot;
+    return 0;
+}
+int ygpu_indelcall_collect(ygpu_ctx *full, ygpu_indel_call *calls)
+{
+    if (!full || !full->stream) return YGPU_EINVAL;
+    if (!full->icHaveCalls) { full->err = "ygpu_indelcall_collect: ygpu_indelcall_size has not been called on this context"; return YGPU_EINVAL; }
+    if (!full->icCalls) return 0;
+    if (!calls || !full->icOut.p) return YGPU_EINVAL;
+    PfSide *ctx = &full->pf;
+    tlsPfFailed = full;
+    HIPCHK(hipSetDevice(full->device));
+    HIPCHK(hipMemcpyAsync(calls, full->icOut.p, sizeof(ygpu_indel_call) * full->icCalls, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
+    tlsPfFailed = nullptr;
+    std::sort(calls, calls + full->icCalls, [](const ygpu_indel_call &a, const ygpu_indel_call &b) {
+        return yindel::keyLess(yindel::Key{a.w0, a.w1, a.w2}, yindel::Key{b.w0, b.w1, b.w2}); });
     return 0;
 }
 // ---- the error profile (eprofile_stage.h; the contract is in ../eprofile_core.h) ------------------------------------------------------------------------------

@@ -81,7 +81,17 @@ static void usage(FILE *o)
           "       QUAL >= -snvqual.  Indels are not called (-oid holds them).  The counts are the pileup's (-opu; 28 bytes of device memory per reference base per\n"
           "       GPU, made for -osnv alone as well, with -puq as its gate); the sites are judged on the device and only the calls leave it.  With -gpus N the\n"
           "       other devices' candidate sites are added to the first one's array before that, which moves what -opu moves.  YAHA_HOST_SNV=1: judged on the\n"
-          "       host.  Errors in these five options leave with exit code 3.\n", o);
+          "       host.  Errors in these five options leave with exit code 3.\n"
+          "  indels  : [-oindel callsFile|stdout] [-inderr errorPerMille (50)] [-indmin minAltReads (2)] [-inddp minDepth (4)] [-indqual minQual (20)]\n"
+          "            [-indshift maxShift (256)] [-puq minMapQ (0)]\n"
+          "       the insertions and deletions of the printed records as genotyped calls, VCF 4.2 with one sample, written after the last alignment.  Every\n"
+          "       allele -oid would list (any length, gate -puq) is moved left along the reference while its last base equals the base before it, at most\n"
+          "       -indshift bases (0: not at all) and never out of its sequence or across an N; alleles that become equal are one, their records add up.  POS is\n"
+          "       the base before the event (the anchor).  d reads cover the anchor (A C G T N del of the pileup there), a carry the allele, r = d - a do not:\n"
+          "       0/0, 0/1 and 1/1 cost r cM + a cE, (r + a) cH and r cE + a cM in 1/100 phred, the costs derived from -inderr (22, 1301, 301 at 50); GT, QUAL\n"
+          "       and GQ as for -osnv.  A line needs GT 0/1 or 1/1, a >= -indmin, d >= -inddp and QUAL >= -indqual.  Insertions of more than 42 bases are\n"
+          "       not called.  Shares the arrays of -opu / -osnv and the table of -oid (which must then run with -idlen 1 and -idq equal to -puq); normalised,\n"
+          "       merged and judged on the device, only the calls leave it.  YAHA_HOST_INDELCALL=1: on the host.  Errors in these options leave with exit code 3.\n", o);
 }
 
 static bool parseBool(const char *s, const char *key, bool &out)
@@ -213,6 +223,17 @@ int parseArgs(int argc, char **argv, Args &a)
         else if (is("-snvdp")) { if (!parseInt(val(), "-snvdp", a.snvDp)) return kPileupError; a.haveSnvDp = true;
             if (a.snvDp < 1) { fprintf(stderr, "-snvdp must be at least 1 (reads that show A, C, G or T).\n\n"); usage(stderr); return kPileupError; } }
         else if (is("-snvqual")) { if (!parseInt(val(), "-snvqual", a.snvQual)) return kPileupError; a.haveSnvQual = true; }
+        else if (is("-oindel")) { const char *v = val(); a.indFileName = (!strcmp(v, "-stdout")) ? "stdout" : v; a.haveIndel = true;
+            if (a.indFileName.empty()) { fprintf(stderr, "-oindel needs a file name.\n\n"); usage(stderr); return kPileupError; } }
+        else if (is("-inderr")) { if (!parseInt(val(), "-inderr", a.indErr)) return kPileupError; a.haveIndErr = true;
+            if (a.indErr < 1 || a.indErr > 500) { fprintf(stderr, "-inderr must be between 1 and 500 (error in per mille).\n\n"); usage(stderr); return kPileupError; } }
+        else if (is("-indmin")) { if (!parseInt(val(), "-indmin", a.indMin)) return kPileupError; a.haveIndMin = true;
+            if (a.indMin < 1) { fprintf(stderr, "-indmin must be at least 1 (reads that carry the allele).\n\n"); usage(stderr); return kPileupError; } }
+        else if (is("-inddp")) { if (!parseInt(val(), "-inddp", a.indDp)) return kPileupError; a.haveIndDp = true;
+            if (a.indDp < 1) { fprintf(stderr, "-inddp must be at least 1 (reads that cover the anchor base).\n\n"); usage(stderr); return kPileupError; } }
+        else if (is("-indqual")) { if (!parseInt(val(), "-indqual", a.indQual)) return kPileupError; a.haveIndQual = true; }
+        else if (is("-indshift")) { if (!parseInt(val(), "-indshift", a.indShift)) return kPileupError; a.haveIndShift = true;
+            if (a.indShift > 65535) { fprintf(stderr, "-indshift must be between 0 and 65535 (bases an allele may move).\n\n"); usage(stderr); return kPileupError; } }
         else { fprintf(stderr, "%s is not a valid option.\n\n", k); usage(stderr); return 2; }
     }
     a.query = query; a.index = index && !query;
@@ -236,7 +257,8 @@ int parseArgs(int argc, char **argv, Args &a)
     if (a.haveBp && a.bpFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout"))) {
         fprintf(stderr, "-obp stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return 3; }
     // the allele pileup: the same rules, its errors with an exit code of their own (3)
-    if (!a.havePu && (a.havePuMin || (a.havePuQ && !a.haveSnv))) { fprintf(stderr, "-pumin needs -opu, -puq needs -opu or -osnv.\n\n"); usage(stderr); return kPileupError; }
+    if (!a.havePu && (a.havePuMin || (a.havePuQ && !a.haveSnv && !a.haveIndel))) { fprintf(stderr, "-pumin needs -opu, -puq needs -opu, -osnv or -oindel.\n\n"); usage(stderr);
+        return kPileupError; }
     if (a.havePu && !query) { fprintf(stderr, "-opu is an output of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return kPileupError; }
     if (a.havePu && a.puFileName == "stdout" && (!a.haveO || a.ofileName == "stdout")) {
         fprintf(stderr, "-opu stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
@@ -267,6 +289,19 @@ int parseArgs(int argc, char **argv, Args &a)
     if (a.haveSnv && a.snvFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout") || (a.haveBp && a.bpFileName == "stdout")
         || (a.havePu && a.puFileName == "stdout") || (a.haveId && a.idFileName == "stdout") || (a.haveEp && a.epFileName == "stdout"))) {
         fprintf(stderr, "-osnv stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
+    // the indel calls: the same rules once more (exit code 3); they stand on the pileup's gate -puq and on alleles of every length counted with that gate
+    if (!a.haveIndel && (a.haveIndErr || a.haveIndMin || a.haveIndDp || a.haveIndQual || a.haveIndShift)) {
+        fprintf(stderr, "-inderr, -indmin, -inddp, -indqual and -indshift need -oindel.\n\n"); usage(stderr); return kPileupError; }
+    if (a.haveIndel && !query) { fprintf(stderr, "-oindel is an output of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return kPileupError; }
+    if (a.haveIndel && a.haveId && (a.idLen != 1 || a.idMinQ != a.puMinQ)) {
+        fprintf(stderr, "-oindel shares the alleles of -oid: beside it -oid must run with -idlen 1 and -idq equal to -puq (%d).\n\n", a.puMinQ); usage(stderr); return kPileupError;
+            }
+    if (a.haveIndel && a.indFileName == "stdout" && (!a.haveO || a.ofileName == "stdout")) {
+        fprintf(stderr, "-oindel stdout: the alignments already go to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
+    if (a.haveIndel && a.indFileName == "stdout" && ((a.haveCov && a.covFileName == "stdout") || (a.haveEv && a.evFileName == "stdout") || (a.haveBp && a.bpFileName == "stdout")
+        || (a.havePu && a.puFileName == "stdout") || (a.haveId && a.idFileName == "stdout") || (a.haveEp && a.epFileName == "stdout")
+        || (a.haveSnv && a.snvFileName == "stdout"))) {
+        fprintf(stderr, "-oindel stdout: another track already goes to standard output; give one of them a file.\n\n"); usage(stderr); return kPileupError; }
     // the sorted BAM: an option of -obh / -obs with a file of its own beside theirs
     if (a.haveSortMem && !a.bamSort) { fprintf(stderr, "-sortmem needs -obsort.\n\n"); usage(stderr); return 3; }
     if (a.bamSort && !query) { fprintf(stderr, "-obsort is an option of query alignment; it is not allowed during index creation.\n\n"); usage(stderr); return 3; }
@@ -345,6 +380,8 @@ std::string samHeader(const Args &a, const Genome &g)                   // outpu
     if (a.haveId) { snprintf(buf, sizeof buf, " -idmin %d -idlen %d -idq %d", a.idMin, a.idLen, a.idMinQ); h += " -oid " + a.idFileName + buf; }
     if (a.haveEp) { snprintf(buf, sizeof buf, " -epq %d", a.epMinQ); h += " -oep " + a.epFileName + buf; }
     if (a.haveSnv) { snprintf(buf, sizeof buf, " -snverr %d -snvmin %d -snvdp %d -snvqual %d", a.snvErr, a.snvMin, a.snvDp, a.snvQual); h += " -osnv " + a.snvFileName + buf; }
+    if (a.haveIndel) { snprintf(buf, sizeof buf, " -inderr %d -indmin %d -inddp %d -indqual %d -indshift %d", a.indErr, a.indMin, a.indDp, a.indQual, a.indShift);
+        h += " -oindel " + a.indFileName + buf; }
     h += "\n";
     return h;
 }

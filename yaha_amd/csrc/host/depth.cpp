@@ -52,6 +52,7 @@ void BinnedTrack::feeders(std::vector<ygpu_ctx *> &ctx, std::vector<int> &dev) c
 bool BinnedTrack::finish(FILE *mainOut, FILE *log, bool timing)
 {
     auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    if (quietFor) return true;                                               // (its array is read where it lies, by the output it serves)
     std::string terr; bool ok = true; std::vector<ygpu_ctx *> feedCtx; std::vector<int> feedDev;
     feeders(feedCtx, feedDev);
     const double m0 = now();
@@ -67,6 +68,7 @@ bool BinnedTrack::finish(FILE *mainOut, FILE *log, bool timing)
 
 void BinnedTrack::stats(std::string &line) const
 {
+    if (quietFor) return;
     char t[512]; snprintf(t, sizeof t, names.statsFmt, (unsigned long long)nBins, (unsigned long long)devRecords, (unsigned long long)hostRecords, (unsigned long long)sum());
     line += t; line += extraStats();
 }

@@ -26,6 +26,7 @@ bool IndelKeyLess::operator()(const IndelKey &a, const IndelKey &b) const { retu
 bool IndelTrack::setup(const Args &a, const Genome &g, int, int nContexts, std::string &err)
 {
     genome = &g; file = a.idFileName; minMapq = (uint32_t)a.idMinQ; minLen = (uint32_t)a.idLen; minCount = (uint32_t)a.idMin;
+    if (quietFor) { minMapq = (uint32_t)a.puMinQ; minLen = 1; }             // (what the indel calls take: every length, the pileup's gate)
     enabled.assign((size_t)nContexts, CtxAt{nullptr, 0, 0, 0});
     capacity = yindel::tableCapacity(a.batchReads > 0 ? std::min<uint64_t>((uint64_t)a.batchReads * (uint64_t)std::max(1, a.maxQueryLength), (uint64_t)16 << 20)
         : (uint64_t)16 << 20);
@@ -99,9 +100,10 @@ bool IndelTrack::finish(FILE *mainOut, FILE *log, bool)
     std::string ierr; bool ok = true;
     for (const CtxAt &at : enabled) if (at.ctx && ok) {
         const int rc = deviceDrain(at.ctx, false, ierr);
-        if (rc != 0) { fprintf(log, "-oid: collecting the indel table of context %d failed (%d): %s\n", at.index, rc, ierr.c_str()); ok = false; }
+        if (rc != 0) { fprintf(log, "%s: collecting the indel table of context %d failed (%d): %s\n", name(), at.index, rc, ierr.c_str()); ok = false; }
     }
-    if (devLost) { fprintf(log, "-oid: %llu indel events found no entry in a device table -- the file would be incomplete.\n", (unsigned long long)devLost); ok = false; }
+    if (devLost) { fprintf(log, "%s: %llu indel events found no entry in a device table -- the file would be incomplete.\n", name(), (unsigned long long)devLost); ok = false; }
+    if (quietFor) return ok;
     if (fflush(mainOut) != 0) ok = false;
     if (ok && !write(file.c_str(), *genome, ierr)) { fprintf(log, "%s\n", ierr.c_str()); ok = false; }
     return ok;
@@ -109,6 +111,7 @@ bool IndelTrack::finish(FILE *mainOut, FILE *log, bool)
 
 void IndelTrack::stats(std::string &line) const
 {
+    if (quietFor) return;
     char t[512]; snprintf(t, sizeof t, ", \"indel_device_records\": %llu, \"indel_host_records\": %llu, \"indel_events\": %llu, \"indel_alleles\": %llu, "
         "\"indel_lines\": %llu, \"indel_drains\": %llu, \"indel_lost\": %llu", (unsigned long long)devRecords, (unsigned long long)hostRecords,
         (unsigned long long)(devEvents + hostEvents), (unsigned long long)alleles.size(), (unsigned long long)nLines, (unsigned long long)drains, (unsigned long long)devLost);

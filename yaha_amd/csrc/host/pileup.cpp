@@ -23,6 +23,7 @@ __attribute__((weak)) int ygpu_pileup_collect(ygpu_ctx *ctx, uint32_t *counts, u
 __attribute__((weak)) int ygpu_pileup_candidates_size(ygpu_ctx *ctx, uint64_t *n);
 __attribute__((weak)) int ygpu_pileup_candidates_collect(ygpu_ctx *ctx, uint32_t *slots);
 __attribute__((weak)) int ygpu_pileup_gather(ygpu_ctx *ctx, const uint32_t *slots, uint64_t n, uint32_t *rows);
+__attribute__((weak)) int ygpu_pileup_add(ygpu_ctx *ctx, const uint32_t *slots, const uint32_t *rows, uint64_t n);
 }
 
 namespace yaha {
@@ -150,6 +151,47 @@ void PileupTrack::hostRows(std::vector<uint32_t> &slots, std::vector<uint32_t> &
             if (r[0] | r[1] | r[2] | r[3] | r[4] | r[5] | r[6]) { slots.push_back((uint32_t)s); rows.insert(rows.end(), r, r + ypileup::NCH); }
         }
     }
+}
+
+int PileupTrack::foldOnce(ygpu_ctx *const *feeders, int n, bool withHost, const std::vector<uint32_t> *at, uint64_t *folded, bool *anyAdded, ygpu_ctx **bad)
+{
+    if (n < 1 || ygpu_pileup_add == nullptr) return YGPU_ENODEV;
+    ygpu_ctx *const home = feeders[0]; std::vector<uint32_t> slots, rows;
+    if (withHost && !hostFolded) {
+        hostRows(slots, rows);
+        if (!slots.empty()) { *anyAdded = true; const int rc = ygpu_pileup_add(home, slots.data(), rows.data(), slots.size()); if (rc != 0) { *bad = home; return rc; } }
+        hostFolded = true; *folded += slots.size();
+    }
+    if (n > 1 && at) {
+        std::vector<uint32_t> want(at->size());
+        want.resize((size_t)(std::set_difference(at->begin(), at->end(), othersFolded.begin(), othersFolded.end(), want.begin()) - want.begin()));
+        for (int k = 1; k < n && !want.empty(); k++) {
+            rows.assign(want.size() * ypileup::NCH + 1, 0);
+            int rc = ygpu_pileup_gather(feeders[k], want.data(), want.size(), rows.data()); if (rc != 0) { *bad = feeders[k]; return rc; }
+            *anyAdded = true; rc = ygpu_pileup_add(home, want.data(), rows.data(), want.size()); if (rc != 0) { *bad = home; return rc; }
+            *folded += want.size();
+        }
+        std::vector<uint32_t> merged(othersFolded.size() + want.size());
+        merged.resize((size_t)(std::set_union(othersFolded.begin(), othersFolded.end(), want.begin(), want.end(), merged.begin()) - merged.begin()));
+        othersFolded.swap(merged);
+    }
+    return 0;
+}
+
+int PileupTrack::rowsAt(ygpu_ctx *const *feeders, int n, const std::vector<uint32_t> &slots, std::vector<uint32_t> &rows, ygpu_ctx **bad)
+{
+    rows.assign(slots.size() * ypileup::NCH + 1, 0); std::vector<uint32_t> part;
+    if (!hostFolded) for (size_t i = 0; i < slots.size(); i++) if (slots[i] < nBins) if (const uint32_t *own = row(slots[i]))
+        for (int ch = 0; ch < ypileup::NCH; ch++) rows[i * ypileup::NCH + ch] += own[ch];
+    for (int k = 0; k < n && !slots.empty(); k++) {
+        part.assign(slots.size() * ypileup::NCH + 1, 0);
+        const int rc = ygpu_pileup_gather(feeders[k], slots.data(), slots.size(), part.data()); if (rc != 0) { *bad = feeders[k]; return rc; }
+        for (size_t i = 0; i < slots.size(); i++) {
+            if (k > 0 && std::binary_search(othersFolded.begin(), othersFolded.end(), slots[i])) continue;      // (already in the home image's row)
+            for (int ch = 0; ch < ypileup::NCH; ch++) rows[i * ypileup::NCH + ch] += part[i * ypileup::NCH + ch];
+        }
+    }
+    return 0;
 }
 
 std::string PileupTrack::mergeNote() const

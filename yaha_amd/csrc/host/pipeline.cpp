@@ -29,7 +29,8 @@ namespace yaha {
 // ---- what a run writes ------------------------------------------------------------------------------------------------------------------------------------------
 // The side outputs the options ask for, in the order their files are written in and their keys stand in the stats line: the binned tracks (depth.cpp,
 // events.cpp, pileup.cpp), the breakpoint calls (junctions.cpp), the indel alleles (indels.cpp), the error profile (eprofile.cpp), the SNV calls (snv.cpp: they
-// judge the run's pileup -- the -opu track's if there is one, which has then written its table before them).  A new kind is one line here.
+// judge the run's pileup -- the -opu track's if there is one, which has then written its table before them), the indel calls (indelcalls.cpp).  A new kind is
+// one line here.
 static std::vector<std::unique_ptr<SideOutput>> makeSideOutputs(const Args &a)
 {
     std::vector<std::unique_ptr<SideOutput>> o;
@@ -38,9 +39,19 @@ static std::vector<std::unique_ptr<SideOutput>> makeSideOutputs(const Args &a)
     PileupTrack *pu = nullptr;
     if (a.havePu) o.emplace_back(pu = new PileupTrack);
     if (a.haveBp) o.emplace_back(new JunctionTrack);
-    if (a.haveId) o.emplace_back(new IndelTrack);
+    IndelTrack *id = nullptr;
+    if (a.haveId) o.emplace_back(id = new IndelTrack);
     if (a.haveEp) o.emplace_back(new EProfileTrack);
-    if (a.haveSnv) o.emplace_back(new SnvTrack(pu));
+    SnvTrack *snv = nullptr;
+    if (a.haveSnv) o.emplace_back(snv = new SnvTrack(pu));
+    // the indel calls stand on a pileup and on the run's indel alleles: the tracks above where the options gave them, otherwise quiet ones of their own, listed
+    // before them so that their finish has run
+    if (a.haveIndel) {
+        PileupTrack *ipu = pu;
+        if (!ipu && !snv) { o.emplace_back(ipu = new PileupTrack); ipu->quietFor = "-oindel"; }
+        if (!id) { o.emplace_back(id = new IndelTrack); id->quietFor = "-oindel"; }
+        o.emplace_back(new IndelCallTrack(ipu, snv, id));
+    }
     return o;
 }
 // (the main output -- SAM / Blast8 text, BAM, sorted BAM -- is makeRecordSink's choice, bam.cpp)

@@ -92,6 +92,11 @@ int yaha_session_snv_params(yaha_session *s, ygpu_snv_params *p)
     if (!s || !p) return YGPU_EINVAL;
     snvParamsFromArgs(s->args, *p); return 0;
 }
+int yaha_session_indelcall_params(yaha_session *s, ygpu_indelcall_params *p)
+{
+    if (!s || !p) return YGPU_EINVAL;
+    indelcallParamsFromArgs(s->args, *p); return 0;
+}
 int yaha_session_indel_params(yaha_session *s, ygpu_indel_params *p)
 {
     if (!s || !p) return YGPU_EINVAL;

@@ -58,22 +58,16 @@ int SnvTrack::callOnDevice(PileupTrack &pu, ygpu_ctx *const *feeders, int n, int
     ygpu_ctx *const home = feeders[0]; bool anyAdded = false; int rc = 0;
     auto failed = [&](ygpu_ctx *c) { err = ygpu_last_error(c); *folded = anyAdded ? 2 : 0; return rc; };
     const double t0 = nowMs();
-    std::vector<uint32_t> slots, rows;
-    pu.hostRows(slots, rows);
-    if (!slots.empty()) { anyAdded = true; rc = ygpu_pileup_add(home, slots.data(), rows.data(), slots.size()); if (rc != 0) return failed(home); }
-    foldedSlots = slots.size();
+    // (through the pileup track, which remembers what has been folded: the indel calls read the same array after this and must add nothing twice)
+    ygpu_ctx *bad = home; foldedSlots = 0;
+    rc = pu.foldOnce(feeders, n, true, nullptr, &foldedSlots, &anyAdded, &bad); if (rc != 0) return failed(bad);
     // The other images: a call's counts must be the sum over ALL sources, the reference's count included -- and an image whose reads all agree with the reference
     // at a slot does not list it.  So the slots are the union of every source's candidates (the home image's and the host's too), and every other image's rows
     // THERE are folded.  A slot outside the union has no disagreeing read in any source: a = 0 in the sum, GT = 0, never a call, whatever part of r it holds.
     if (n > 1) {
-        std::vector<uint32_t> all; int bad = -1;
-        rc = pu.candidatesUnion(feeders, n, true, *genome, all, &bad, err); if (rc != 0) { *folded = anyAdded ? 2 : 0; return rc; }
-        for (int k = 1; k < n && !all.empty(); k++) {
-            rows.assign(all.size() * ypileup::NCH + 1, 0);
-            rc = ygpu_pileup_gather(feeders[k], all.data(), all.size(), rows.data()); if (rc != 0) return failed(feeders[k]);
-            anyAdded = true; rc = ygpu_pileup_add(home, all.data(), rows.data(), all.size()); if (rc != 0) return failed(home);
-            foldedSlots += all.size();
-        }
+        std::vector<uint32_t> all; int badImage = -1;
+        rc = pu.candidatesUnion(feeders, n, true, *genome, all, &badImage, err); if (rc != 0) { *folded = anyAdded ? 2 : 0; return rc; }
+        rc = pu.foldOnce(feeders, n, false, &all, &foldedSlots, &anyAdded, &bad); if (rc != 0) return failed(bad);
     }
     *folded = 1;
     const double t1 = nowMs(); msFold = t1 - t0;

@@ -95,6 +95,10 @@ struct Args {
     // allele), -snvdp D (depth), -snvqual Q (QUAL in phred); the mapping-quality gate is the pileup's -puq
     bool haveSnv = false, haveSnvErr = false, haveSnvMin = false, haveSnvDp = false, haveSnvQual = false; std::string snvFileName;
     int snvErr = 100, snvMin = 2, snvDp = 4, snvQual = 20;
+    // indel calls: -oindel FILE (VCF 4.2: the run's indel alleles left-normalised, merged and genotyped at their anchor base), -inderr E (per mille), -indmin N
+    // (reads that carry the allele), -inddp D (reads that cover the anchor), -indqual Q, -indshift S (bases an allele may move; 0: as the aligner put it); gate -puq
+    bool haveIndel = false, haveIndErr = false, haveIndMin = false, haveIndDp = false, haveIndQual = false, haveIndShift = false; std::string indFileName;
+    int indErr = 50, indMin = 2, indDp = 4, indQual = 20, indShift = 256;
     bool query = false, index = true, compress = false, uncompress = false;   // -c / -u: .fa -> .nib2 / .nib2 -> .fasta only (Main.c:284-293, non-user builds of the reference)
 };
 void postProcessArgs(Args &a, bool query);                                  // AlignArgs.c:108-169
@@ -102,6 +106,7 @@ void postProcessArgs(Args &a, bool query);                                  // A
 int  parseArgs(int argc, char **argv, Args &a);                            // Main.c:187-565
 void paramsFromArgs(const Args &a, ygpu_params &p);
 void snvParamsFromArgs(const Args &a, ygpu_snv_params &p);                  // snv.cpp: the three costs from -snverr, the three thresholds
+void indelcallParamsFromArgs(const Args &a, ygpu_indelcall_params &p);      // indelcalls.cpp: the three costs from -inderr, the three thresholds
 std::string samHeader(const Args &a, const Genome &g);                      // AlignOutput.c:30-111
 
 // ---- reads (reference Query.c:63-228, QueryState.c:172-187) ---------------------------------------------
@@ -263,7 +268,8 @@ struct BinnedTrack : SideOutput {
     uint64_t devRecords = 0, devSkipped = 0, devDropped = 0, devHandedBack = 0;
     BinnedTrack(const BinnedTrack &) = delete; BinnedTrack &operator=(const BinnedTrack &) = delete;
     ~BinnedTrack() override { free(data); }
-    const char *name() const override { return names.fileOpt; }
+    const char *quietFor = nullptr;                                       // set: the track serves that option alone -- no file, no keys of the stats line, no merge
+    const char *name() const override { return quietFor ? quietFor : names.fileOpt; }
     int  enable(const CtxAt &at) override;
     int  beforeFilter(const CtxAt &at, size_t) override;                  // (the image's feeder)
     bool finish(FILE *mainOut, FILE *log, bool timing) override;
@@ -331,6 +337,14 @@ struct PileupTrack : BinnedTrack {                                        // (a 
     int  candidatesUnion(ygpu_ctx *const *feeders, int n, bool withHost, const Genome &g, std::vector<uint32_t> &all, int *failed, std::string &err);      // the union alone
     // the host's counts as a list for ygpu_pileup_add: the slots of its blocks that hold something, ascending, and their rows
     void hostRows(std::vector<uint32_t> &slots, std::vector<uint32_t> &rows) const;
+    // Folds into feeders[0]'s array (ygpu_pileup_add) what the callers -- the SNV calls, the indel calls -- need summed there, each thing ONCE a run whoever asks
+    // first: the host's rows (withHost) unless they have been folded, and every other image's rows at those of `at` (ascending, distinct; may be null) that
+    // have not been.  *folded += list entries added; *anyAdded: the array is no longer the image's own.  0, or the device's code with *bad = the context.
+    int  foldOnce(ygpu_ctx *const *feeders, int n, bool withHost, const std::vector<uint32_t> *at, uint64_t *folded, bool *anyAdded, ygpu_ctx **bad);
+    // the sources' summed rows at `slots` for a caller on the host, after whatever has been folded: feeders[0]'s array, the others' where they have not been
+    // folded into it, the host's unless they have been
+    int  rowsAt(ygpu_ctx *const *feeders, int n, const std::vector<uint32_t> &slots, std::vector<uint32_t> &rows, ygpu_ctx **bad);
+    bool hostFolded = false; std::vector<uint32_t> othersFolded;          // what foldOnce has done: the host's rows; the slots of the other images (ascending)
     uint64_t sum() const override { return hostCounted + devCounted; }    // (the counts added: the sum over the arrays without reading 28 bytes a base)
     std::string extraStats() const override;
     std::string mergeNote() const override;
@@ -391,7 +405,8 @@ struct IndelTrack : SideOutput {
     uint64_t devRecords = 0, devSkipped = 0, devDropped = 0, devEvents = 0, devHandedBack = 0, devLost = 0, drains = 0, nLines = 0;
     // what a formatter thread gathers of one batch before it merges: the events' keys and what became of the records it walked
     struct Local : Slot { std::vector<IndelKey> keys; uint64_t records = 0, skipped = 0, dropped = 0; };
-    const char *name() const override { return "-oid"; }
+    const char *quietFor = nullptr;                                       // set: the track serves that option alone (-oindel) -- -puq and length 1, no file, no keys
+    const char *name() const override { return quietFor ? quietFor : "-oid"; }
     bool setup(const Args &a, const Genome &g, int nImages, int nContexts, std::string &err) override;      // -idq, -idlen, -idmin; the table's capacity
     int  enable(const CtxAt &at) override;                                // (remembers the context for the end of the run)
     int  beforeFilter(const CtxAt &at, size_t batchBases) override;
@@ -455,6 +470,7 @@ struct SnvTrack : SideOutput {
     bool finish(FILE *mainOut, FILE *log, bool timing) override;
     void stats(std::string &line) const override;
     static bool deviceEntryPoints();                                      // does this build have ygpu_pileup_add and ygpu_snv_*?
+    PileupTrack *pileup() const { return shared ? shared : own.get(); }   // the array it judges (after setup)
     std::vector<ygpu_snv_call> calls;                                     // what the writer prints, ascending (made by finish)
     uint64_t nHet = 0, nHom = 0, foldedSlots = 0; bool onDevice = false;
     bool write(const char *path, std::string &err) const;                 // path "stdout" = standard output
@@ -463,6 +479,32 @@ struct SnvTrack : SideOutput {
     int  callOnHost(PileupTrack &pu, ygpu_ctx *const *feeders, int n, bool withHost, std::string &err);
     PileupTrack *shared; std::unique_ptr<PileupTrack> own; const Genome *genome = nullptr; std::string file, options; ygpu_snv_params P{};
     double msFold = 0, msSelect = 0, msWrite = 0;
+};
+
+// ---- indel calls with genotypes (-oindel; indelcalls.cpp, ../indelcall_core.h) ---------------------------------------------------------------------------------
+// The eighth side output counts nothing itself either: it takes the run's raw indel alleles -- the -oid track's when that runs with -idlen 1 and -idq = -puq,
+// otherwise a quiet IndelTrack the run driver lists before it -- and the run's pileup -- the -opu track's, failing that the one -osnv made, failing that a quiet
+// PileupTrack listed before it.  finish runs after theirs.  On the home image, the first with a feeder: the alleles are normalised and merged
+// (ygpu_indelcall_normalize); what the array lacks is folded in (PileupTrack::foldOnce: the host's rows, and with several images the others' rows at the anchor
+// slots, which the merged alleles are fetched for); the calls are selected and collected (ygpu_indelcall_size / _collect).  Without the entry points (the CPU
+// tier's test doubles), without a feeder, with YAHA_HOST_INDELCALL=1 or when the device step fails before any fold the same core runs on the host over
+// PileupTrack::rowsAt; a fold that failed half-way fails the run.
+struct IndelCallTrack : SideOutput {
+    IndelCallTrack(PileupTrack *pileupTrack, SnvTrack *snvTrack, IndelTrack *indelTrack) : puGiven(pileupTrack), snv(snvTrack), id(indelTrack) {}
+    const char *name() const override { return "-oindel"; }
+    bool setup(const Args &a, const Genome &g, int nImages, int nContexts, std::string &err) override;
+    bool finish(FILE *mainOut, FILE *log, bool timing) override;
+    void stats(std::string &line) const override;
+    static bool deviceEntryPoints();                                      // does this build have ygpu_indelcall_* and the folds?
+    std::vector<ygpu_indel_call> calls;                                   // what the writer prints, in keyLess order (made by finish)
+    uint64_t nHet = 0, nHom = 0, nRaw = 0, nShifted = 0, nMerged = 0, nSkipped = 0, foldedSlots = 0; bool onDevice = false;
+    bool write(const char *path, std::string &err) const;                 // path "stdout" = standard output
+  private:
+    int  callOnDevice(ygpu_ctx *const *feeders, int n, const std::vector<ygpu_indel_entry> &raw, bool *anyAdded, std::string &err);
+    int  callOnHost(ygpu_ctx *const *feeders, int n, const std::vector<ygpu_indel_entry> &raw, std::string &err);
+    PileupTrack *puGiven; SnvTrack *snv; IndelTrack *id; PileupTrack *pu = nullptr; const Genome *genome = nullptr; std::string file, options;
+    ygpu_indelcall_params P{}; uint32_t maxShift = 256; bool foldBroke = false;      // (a fold that failed after it had added something)
+    double msNorm = 0, msFold = 0, msSelect = 0, msWrite = 0;
 };
 
 // ---- the main output of a query run: where the formatted records of the batches go (sam.cpp: SAM / Blast8 text; bam.cpp: BAM, sorted BAM) -----------------
