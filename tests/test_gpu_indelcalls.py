@@ -1,6 +1,6 @@
 """GPU tier: indel calls with genotypes (-oindel) on the device (device/indelcall_stage.h: k_indel_norm left-normalises a raw allele per wave against the
-image's reference and merges into a table, k_indelcall_count / k_indelcall_emit judge every merged allele at its anchor against the image's pileup array).
-The direct cases run the directed set of tests/indelcall_sets.py on an index of the crafted genome, built here; the command-line cases run the variant read
+image's reference and merges into a table, k_select_count / k_select_emit over IndelCallSel (device/select.h) judge every merged allele at its anchor
+against the image's pileup array).  The direct cases run the directed set of tests/indelcall_sets.py on an index of the crafted genome, built here; the command-line cases run the variant read
 set with planted indels on the golden genome.  Every comparison is with tests/indelcall_oracle.py."""
 import json
 import os

@@ -1,6 +1,6 @@
 """GPU tier: SNV calls with genotypes (-osnv) judged on the device from the pileup array (device/snv_stage.h: k_pileup_add folds the other sources into one
-image's array, k_snv_count / k_snv_emit select and judge -- a wave per tile of 2 048 slots, the records written by ballot and population count).  Every
-comparison is with tests/snv_oracle.py over tests/pileup_oracle.py, which recompute the calls from SAM text and the reference FASTA alone, or -- the direct
+image's array, k_select_count / k_select_emit over SnvSel (device/select.h) select and judge -- a wave per tile of 2 048 slots, the records written by
+ballot and population count).  Every comparison is with tests/snv_oracle.py over tests/pileup_oracle.py, which recompute the calls from SAM text and the reference FASTA alone, or -- the direct
 cases -- from the very rows the test folds into an empty array.  The reads of the command-line cases are the variant set snv_oracle.variant_reads makes."""
 import ctypes as C
 import json

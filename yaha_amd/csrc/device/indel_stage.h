@@ -16,10 +16,10 @@
 // spinning, no locks, no LDS; ordinary global atomics.  The lane that turns a w0 from 0 adds 1 to `used`; a lane that has probed `probeLimit` entries in vain
 // adds 1 to `lost` and gives up (the host then answers YGPU_EOVERFLOW).
 //
-// Draining follows the pileup's candidate selection: k_indel_count counts the occupied entries of a tile of 64 x YI_TILE_ROWS entries, an exclusive sum of the
-// tiles' counts (scan.h) places them, k_indel_emit writes the occupied entries in ascending table index by ballot and population count.
+// Draining: IndelDrainSel picks the occupied entries and leaves them in ascending table index, through the tile selection of select.h.
 #pragma once
 #include "track_stage.h"
+#include "select.h"
 #include "../indel_core.h"
 
 #define YI_PROBE_LIMIT 1024u
@@ -84,31 +84,9 @@ __global__ void __launch_bounds__(256) k_indel_clumps(IndelArgs A, const ygpu_ou
 }
 
 // ---- draining: the occupied entries, ascending table index ------------------------------------------------------------------------------------------------------
-#define YI_TILE_ROWS 32u
-#define YI_TILE (64u * YI_TILE_ROWS)
-struct IndelDrainArgs { const ygpu_indel_entry *table; uint64_t capacity; uint32_t nTiles; uint32_t *cnt; const uint32_t *start; ygpu_indel_entry *out; uint32_t cap; };
-__global__ void __launch_bounds__(256) k_indel_count(IndelDrainArgs A)
-{
-    const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
-    if (t >= A.nTiles) return;
-    uint32_t n = 0;
-    for (uint32_t r = 0; r < YI_TILE_ROWS; r++) {
-        const uint64_t i = (uint64_t)t * YI_TILE + r * 64u + lane;
-        n += (uint32_t)__popcll(__ballot(i < A.capacity && A.table[i].w0 != 0ull));
-    }
-    if (lane == 0) A.cnt[t] = n;
-}
-__global__ void __launch_bounds__(256) k_indel_emit(IndelDrainArgs A)
-{
-    const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
-    if (t >= A.nTiles) return;
-    uint32_t at = A.start[t];
-    if (A.start[t + 1] == at) return;
-    for (uint32_t r = 0; r < YI_TILE_ROWS; r++) {
-        const uint64_t i = (uint64_t)t * YI_TILE + r * 64u + lane; const bool is = i < A.capacity && A.table[i].w0 != 0ull;
-        const unsigned long long m = __ballot(is);
-        const uint32_t pos = at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (is && pos < A.cap) A.out[pos] = A.table[i];
-        at += (uint32_t)__popcll(m);
-    }
-}
+struct IndelDrainSel {
+    static constexpr uint32_t ROWS = 32, COUNT_UNROLL = 1; using Rec = NoRec;
+    const ygpu_indel_entry *table; uint64_t capacity; ygpu_indel_entry *out;
+    __device__ __forceinline__ bool pick(uint64_t i, Rec &) const { return i < capacity && table[i].w0 != 0ull; }
+    __device__ __forceinline__ void put(uint32_t pos, uint64_t i, const Rec &) const { out[pos] = table[i]; }
+};

@@ -12,12 +12,11 @@
 // The merge table is the context's own, made for the call: open addressing, linear probing, a power of two of at least twice the raw alleles, entries of 32
 // bytes {w0, w1, w2, a 64-bit count}.  The insert is indel_stage.h's compare-and-swap on the three words; the count is a 64-bit atomic add (at most 2^32 raw
 // alleles of at most 2^32 - 1 each: no wrap), saturated to 32 bits when the table is drained.  Which ENTRY a key lands in depends on who came first; the set
-// of keys and every sum do not.  Draining is the indel table's (k_indel_count, the exclusive sum) with an emit of its own that saturates the count.
+// of keys and every sum do not.  Draining is the indel table's with a store of its own that saturates the count (IndelMergeDrainSel).
 //
-// k_indelcall_count / k_indelcall_emit: a lane per merged allele, 64 x YC_TILE_ROWS alleles a wave.  The lane loads its allele and the seven words of its
-// anchor's row, looks up the anchor's reference code and runs yindelcall::judge; calls are counted per tile, placed by the exclusive sum and written by ballot
-// and population count, as k_snv_* and k_indel_emit write theirs.  The kernels are small and latency-bound -- a run has thousands of alleles, not millions; their
-// cost on a large run has not been measured.
+// IndelCallSel: a lane per merged allele, 64 x 8 alleles a wave, through the tile selection of select.h.  The lane loads its allele and the seven words of its
+// anchor's row, looks up the anchor's reference code and runs yindelcall::judge.  The kernels are small and latency-bound -- a run has thousands of alleles,
+// not millions; their cost on a large run has not been measured.
 #pragma once
 #include "indel_stage.h"
 #include "../indelcall_core.h"
@@ -77,68 +76,38 @@ __global__ void __launch_bounds__(256) k_indel_norm(IndelNormArgs A)
     if (lane == 0) { if (s) atomicAdd(A.stats, 1ull); indelMergeInsert(A, o, e.count); }
 }
 
-// ---- draining the merge table: indel_stage.h's count and sums, an emit that saturates the 64-bit count ----------------------------------------------------------
-__global__ void __launch_bounds__(256) k_indelcall_drain(IndelDrainArgs A)
-{
-    const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
-    if (t >= A.nTiles) return;
-    uint32_t at = A.start[t];
-    if (A.start[t + 1] == at) return;
-    for (uint32_t r = 0; r < YI_TILE_ROWS; r++) {
-        const uint64_t i = (uint64_t)t * YI_TILE + r * 64u + lane; const bool is = i < A.capacity && A.table[i].w0 != 0ull;
-        const unsigned long long m = __ballot(is);
-        const uint32_t pos = at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (is && pos < A.cap) { ygpu_indel_entry e = A.table[i]; if (e.zero) { e.count = 0xFFFFFFFFu; e.zero = 0u; } A.out[pos] = e; }
-        at += (uint32_t)__popcll(m);
+// ---- draining the merge table: indel_stage.h's pick, a store that saturates the 64-bit count ---------------------------------------------------------------------
+struct IndelMergeDrainSel : IndelDrainSel {
+    __device__ __forceinline__ void put(uint32_t pos, uint64_t i, const Rec &) const
+    {
+        ygpu_indel_entry e = table[i]; if (e.zero) { e.count = 0xFFFFFFFFu; e.zero = 0u; } out[pos] = e;
     }
-}
+};
 
 // ---- the selection: every merged allele judged at its anchor ----------------------------------------------------------------------------------------------------
-#define YC_TILE_ROWS 8u
-#define YC_TILE (64u * YC_TILE_ROWS)
-struct IndelCallArgs {
+struct IndelCallSel {
+    static constexpr uint32_t ROWS = 8, COUNT_UNROLL = 4; using Rec = ygpu_indel_call;
     ydepth::Layout L; const uint32_t *pu; uint32_t nSlots; const uint8_t *bases; uint64_t nBaseBytes;      // the image's array and packed reference
-    const ygpu_indel_entry *alleles; uint32_t n, nTiles;
+    const ygpu_indel_entry *alleles; uint32_t n;
     ygpu_indelcall_params P;
-    uint32_t *cnt; const uint32_t *start; ygpu_indel_call *out; uint32_t cap;
-};
-__device__ __forceinline__ bool indelCall(const IndelCallArgs &A, uint64_t i, ygpu_indel_call *c)
-{
-    if (i >= A.n) return false;
-    const ygpu_indel_entry e = A.alleles[i];
-    yindel::Key k; k.w0 = e.w0; k.w1 = e.w1; k.w2 = e.w2;
-    const uint32_t p = yindel::slotOfKey(k);
-    if (p == 0u || p > A.nSlots) return false;                                   // (a normalised allele always has an anchor inside the array)
-    uint32_t row[ypileup::NCH];
+    ygpu_indel_call *out;
+    __device__ __forceinline__ bool pick(uint64_t i, Rec &c) const
+    {
+        if (i >= n) return false;
+        const ygpu_indel_entry e = alleles[i];
+        yindel::Key k; k.w0 = e.w0; k.w1 = e.w1; k.w2 = e.w2;
+        const uint32_t p = yindel::slotOfKey(k);
+        if (p == 0u || p > nSlots) return false;                                 // (a normalised allele always has an anchor inside the array)
+        uint32_t row[ypileup::NCH];
 #pragma unroll
-    for (int ch = 0; ch < ypileup::NCH; ch++) row[ch] = A.pu[(size_t)(p - 1u) * ypileup::NCH + ch];
-    return yindelcall::judgeAt(A.L, A.bases, A.nBaseBytes, k, e.count, row, A.P, c);
-}
-__global__ void __launch_bounds__(256) k_indelcall_count(IndelCallArgs A)
-{
-    const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
-    if (t >= A.nTiles) return;
-    uint32_t n = 0;
-#pragma unroll 4
-    for (uint32_t r = 0; r < YC_TILE_ROWS; r++) { ygpu_indel_call c; n += (uint32_t)__popcll(__ballot(indelCall(A, (uint64_t)t * YC_TILE + r * 64u + lane, &c))); }
-    if (lane == 0) A.cnt[t] = n;
-}
-__global__ void __launch_bounds__(256) k_indelcall_emit(IndelCallArgs A)
-{
-    const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
-    if (t >= A.nTiles) return;
-    uint32_t at = A.start[t];
-    if (A.start[t + 1] == at) return;
-    for (uint32_t r = 0; r < YC_TILE_ROWS; r++) {
-        ygpu_indel_call c; const bool is = indelCall(A, (uint64_t)t * YC_TILE + r * 64u + lane, &c);
-        const unsigned long long m = __ballot(is);
-        const uint32_t pos = at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (is && pos < A.cap) {                                             // 64 bytes, 16-byte aligned: four 16-byte stores
-            uint4 *const o = reinterpret_cast<uint4 *>(A.out + pos);
-            o[0] = make_uint4((uint32_t)c.w0, (uint32_t)(c.w0 >> 32), (uint32_t)c.w1, (uint32_t)(c.w1 >> 32));
-            o[1] = make_uint4((uint32_t)c.w2, (uint32_t)(c.w2 >> 32), c.alt_count, c.ref_count);
-            o[2] = make_uint4(c.depth, c.qual, c.gq, c.pl[0]); o[3] = make_uint4(c.pl[1], c.pl[2], c.info, 0u);
-        }
-        at += (uint32_t)__popcll(m);
+        for (int ch = 0; ch < ypileup::NCH; ch++) row[ch] = pu[(size_t)(p - 1u) * ypileup::NCH + ch];
+        return yindelcall::judgeAt(L, bases, nBaseBytes, k, e.count, row, P, &c);
     }
-}
+    __device__ __forceinline__ void put(uint32_t pos, uint64_t, const Rec &c) const       // 64 bytes, 16-byte aligned: four 16-byte stores
+    {
+        uint4 *const o = reinterpret_cast<uint4 *>(out + pos);
+        o[0] = make_uint4((uint32_t)c.w0, (uint32_t)(c.w0 >> 32), (uint32_t)c.w1, (uint32_t)(c.w1 >> 32));
+        o[1] = make_uint4((uint32_t)c.w2, (uint32_t)(c.w2 >> 32), c.alt_count, c.ref_count);
+        o[2] = make_uint4(c.depth, c.qual, c.gq, c.pl[0]); o[3] = make_uint4(c.pl[1], c.pl[2], c.info, 0u);
+    }
+};

@@ -14,12 +14,12 @@
 // The array is shared by the contexts of an index image: plain global atomicAdd on uint32 (no value returned, device scope), one per aligned base.  At one base
 // a slot nothing can be combined in the wave.
 //
-// The end of the run: k_pileup_count / k_pileup_emit select the slots with nonref >= 1 in ascending order -- a wave takes a tile of 64 x YP_TILE_ROWS
-// neighbouring slots, counts its candidates, an exclusive sum of the tiles' counts (scan.h) places them, and the second pass writes them by ballot and
-// population count, no LDS.  An untouched slot leaves after its seven loads; only a touched one looks the reference base up (the sequence table, then the
-// packed image).  k_pileup_gather writes the seven counts of every slot of a caller's list.
+// The end of the run: CandidateSel selects the slots with nonref >= 1 in ascending order, through the tile selection of select.h.  An untouched slot leaves
+// after its seven loads; only a touched one looks the reference base up (the sequence table, then the packed image).  k_pileup_gather writes the seven counts
+// of every slot of a caller's list.
 #pragma once
 #include "track_stage.h"
+#include "select.h"
 #include "../pileup_core.h"
 
 struct PileupArgs {
@@ -81,43 +81,21 @@ __global__ void __launch_bounds__(256) k_pileup_clumps(PileupArgs P, const ygpu_
 }
 
 // ---- the candidates: slots with nonref >= 1, ascending ---------------------------------------------------------------------------------------------------------
-#define YP_TILE_ROWS 32u
-#define YP_TILE (64u * YP_TILE_ROWS)
-struct CandidateArgs {
-    ydepth::Layout L; const uint32_t *pu; uint32_t nSlots, nTiles; const uint8_t *bases; uint64_t nBaseBytes;      // the image's packed reference
-    uint32_t *cnt; const uint32_t *start; uint32_t *out; uint32_t cap;
-};
-__device__ __forceinline__ bool pileupCandidate(const CandidateArgs &A, uint64_t slot64)
-{
-    if (slot64 >= A.nSlots) return false;
-    const uint32_t slot = (uint32_t)slot64;
-    uint32_t row[ypileup::NCH];
+struct CandidateSel {
+    static constexpr uint32_t ROWS = 32, COUNT_UNROLL = 1; using Rec = NoRec;
+    ydepth::Layout L; const uint32_t *pu; uint32_t nSlots; const uint8_t *bases; uint64_t nBaseBytes;      // the image's array and packed reference
+    uint32_t *out;
+    __device__ __forceinline__ bool pick(uint64_t slot64, Rec &) const
+    {
+        if (slot64 >= nSlots) return false;
+        const uint32_t slot = (uint32_t)slot64;
+        uint32_t row[ypileup::NCH];
 #pragma unroll
-    for (int ch = 0; ch < ypileup::NCH; ch++) row[ch] = A.pu[(size_t)slot * ypileup::NCH + ch];
-    return ypileup::isSiteAt(A.L, A.bases, A.nBaseBytes, slot, row, 1u);
-}
-__global__ void __launch_bounds__(256) k_pileup_count(CandidateArgs A)
-{
-    const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
-    if (t >= A.nTiles) return;
-    uint32_t n = 0;
-    for (uint32_t r = 0; r < YP_TILE_ROWS; r++) n += (uint32_t)__popcll(__ballot(pileupCandidate(A, (uint64_t)t * YP_TILE + r * 64u + lane)));
-    if (lane == 0) A.cnt[t] = n;
-}
-__global__ void __launch_bounds__(256) k_pileup_emit(CandidateArgs A)
-{
-    const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
-    if (t >= A.nTiles) return;
-    uint32_t at = A.start[t];
-    if (A.start[t + 1] == at) return;
-    for (uint32_t r = 0; r < YP_TILE_ROWS; r++) {
-        const uint64_t slot = (uint64_t)t * YP_TILE + r * 64u + lane; const bool is = pileupCandidate(A, slot);
-        const unsigned long long m = __ballot(is);
-        const uint32_t pos = at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (is && pos < A.cap) A.out[pos] = (uint32_t)slot;
-        at += (uint32_t)__popcll(m);
+        for (int ch = 0; ch < ypileup::NCH; ch++) row[ch] = pu[(size_t)slot * ypileup::NCH + ch];
+        return ypileup::isSiteAt(L, bases, nBaseBytes, slot, row, 1u);
     }
-}
+    __device__ __forceinline__ void put(uint32_t pos, uint64_t slot, const Rec &) const { out[pos] = (uint32_t)slot; }
+};
 // rows[i * NCH + ch] = pu[slots[i]][ch] (zero for a slot past the array)
 __global__ void __launch_bounds__(256) k_pileup_gather(const uint32_t *pu, uint32_t nSlots, const uint32_t *slots, uint32_t n, uint32_t *rows)
 {

@@ -121,6 +121,22 @@ static int scanGaveUp(PfSide *ctx, const char *what)
     HIPCHK(streamSync(ctx));
     ctx->err = std::string(what) + ": a look-back of an exclusive sum gave up"; return YGPU_EINTERNAL;
 }
+// ---- the filter side of an entry point ---------------------------------------------------------------------------------------------------------------------------
+// ygpu_last_error answers with the filter side's message (full->pf.err) while tlsPfFailed names the context on this thread, and with full->err otherwise.  The
+// rule, stated here and nowhere else: pfEnter names the context before the first step that may fail on the filter's side -- HIPCHK, ENSURE, KL and the helpers
+// below write that side's message and return with the name standing; pfLeave takes it back on success; pfArgError takes it back for an argument error, whose
+// message is the context's own.
+static PfSide *pfEnter(ygpu_ctx *full) { tlsPfFailed = full; return &full->pf; }
+static int pfLeave() { tlsPfFailed = nullptr; return 0; }
+static int pfArgError(ygpu_ctx *full, const std::string &what) { tlsPfFailed = nullptr; full->err = what; return YGPU_EINVAL; }
+// the last word of a run of exclusive sums -- the total -- with the flag of a look-back that gave up and the caller's own words, in ONE wait
+static int fetchTotal(PfSide *ctx, const uint32_t *last, const char *noun, uint32_t *tot, FetchPiece extra = {nullptr, nullptr, 0})
+{
+    uint32_t scanFail = 0;
+    const FetchPiece pc[3] = {{last, tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1}, extra};
+    const int rc = fetchMany(ctx, pc, extra.n ? 3 : 2); if (rc) return rc;
+    return scanFail ? scanGaveUp(ctx, noun) : 0;
+}
 static ydepth::Layout trackLayout(const TrackImage &T)
 {
     return ydepth::Layout{T.seqStart.as<uint32_t>(), T.seqLength.as<uint32_t>(), T.binBase.as<uint32_t>(), (uint32_t)T.hSeqStart.size(), T.bin, T.minMapq};
@@ -192,7 +208,7 @@ static int postfilterBody(ygpu_ctx *full);
 int ygpu_postfilter(ygpu_ctx *full)
 {
     if (!full || !full->stream) return YGPU_EINVAL;
-    if (!full->pfSnap.load()) { const int rc = ygpu_postfilter_snapshot(full); if (rc) { tlsPfFailed = nullptr; return rc; } }      // (the snapshot's message is the context's own)
+    if (!full->pfSnap.load()) { const int rc = ygpu_postfilter_snapshot(full); if (rc) { pfLeave(); return rc; } }      // (the snapshot's message is the context's own)
     int rc = postfilterBody(full);
     if (rc == 0 && ydCheckStateOn()) {                                       // (debug switch: the post-filter side's own look-back words)
         const DevBuf *const bufs[1] = {&full->pf.scanState}; static const char *const names[1] = {"the post-filter side's look-back state"};
@@ -201,8 +217,8 @@ int ygpu_postfilter(ygpu_ctx *full)
         if (rc) full->oqDone = false;
     }
     full->pfSnap.store(false);
-    tlsPfFailed = rc ? full : nullptr;
-    return rc;
+    if (rc) { pfEnter(full); return rc; }
+    return pfLeave();
 }
 static int postfilterBody(ygpu_ctx *full)
 {
@@ -416,164 +432,140 @@ static int pileupSide(ygpu_ctx *full)
     HIPCHK(hipMemsetAsync(ctx->counters.p, 0, 4 * CNT_N, ctx->stream));
     return 0;
 }
+// The count half of a tile selection (select.h) on the filter's side: the tiles' two buffers sized, the two words behind the counts zeroed, the count pass, the
+// exclusive sums, and ONE wait for the total (with the caller's own words, if it has any).  The buffers are the pileup's (the candidates, the SNV calls) or the
+// indel stage's (both drains, the indel calls).  The emit half is the caller's: sel.out sized from *tot, t->cap set, one launch of k_select_emit<S>.
+enum TileBufs { TILES_PILEUP, TILES_INDEL };
+static dim3 selectGrid(const TileSel &t) { return dim3(gridFor((uint64_t)t.nTiles * 64, 256)); }
+extern "C++" template <class S> static int selectCount(ygpu_ctx *full, TileBufs which, const S &sel, uint64_t nItems, const char *noun, TileSel *t, uint32_t *tot,
+                                          FetchPiece extra = {nullptr, nullptr, 0})
+{
+    PfSide *ctx = &full->pf;
+    const uint32_t nTiles = (uint32_t)((nItems + 64u * S::ROWS - 1) / (64u * S::ROWS));
+    if (which == TILES_PILEUP) { ENSURE(full->puTileCnt, 4ull * (nTiles + 2)); ENSURE(full->puTileStart, 4ull * (nTiles + 2)); }
+    else { ENSURE(full->idTileCnt, 4ull * (nTiles + 2)); ENSURE(full->idTileStart, 4ull * (nTiles + 2)); }
+    uint32_t *const cnt = (which == TILES_PILEUP ? full->puTileCnt : full->idTileCnt).as<uint32_t>();
+    uint32_t *const start = (which == TILES_PILEUP ? full->puTileStart : full->idTileStart).as<uint32_t>();
+    HIPCHK(hipMemsetAsync(cnt + nTiles, 0, 8, ctx->stream));
+    *t = TileSel{nTiles, cnt, start, 0};
+    KL(k_select_count<S>, selectGrid(*t), dim3(256), 0, ctx->stream, sel, *t);
+    const int rc = cubScan(ctx, cnt, start, nTiles + 1); if (rc) return rc;
+    return fetchTotal(ctx, start + nTiles, noun, tot, extra);
+}
+// A selection's records to the caller, on the filter side's stream (no wait for the rest of the device: the selection waited)
+static int collectRecords(ygpu_ctx *full, bool have, const char *notYet, uint64_t n, void *out, const DevBuf &src, size_t recBytes)
+{
+    if (!have) return pfArgError(full, notYet);
+    if (!n) return 0;
+    if (!out || !src.p) return YGPU_EINVAL;
+    PfSide *ctx = pfEnter(full);
+    HIPCHK(hipSetDevice(full->device));
+    HIPCHK(hipMemcpyAsync(out, src.p, recBytes * n, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
+    return pfLeave();
+}
 int ygpu_pileup_candidates_size(ygpu_ctx *full, uint64_t *n)
 {
     if (!full || !full->stream || !n) return YGPU_EINVAL;
-    if (!full->track[TRACK_PILEUP]) { full->err = "ygpu_pileup_candidates_size: ygpu_pileup_enable has not been called on this context"; return YGPU_EINVAL; }
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
+    if (!full->track[TRACK_PILEUP]) return pfArgError(full, "ygpu_pileup_candidates_size: ygpu_pileup_enable has not been called on this context");
+    PfSide *ctx = pfEnter(full);
     HIPCHK(hipSetDevice(full->device));
     HIPCHK(hipDeviceSynchronize());
     const TrackImage &T = *full->track[TRACK_PILEUP];
     full->puHaveCand = false; full->puNCand = 0;
     int rc = pileupSide(full); if (rc) return rc;
-    const uint32_t nSlots = (uint32_t)T.nBins, nTiles = (uint32_t)((T.nBins + YP_TILE - 1) / YP_TILE);
-    ENSURE(full->puTileCnt, 4ull * (nTiles + 2)); ENSURE(full->puTileStart, 4ull * (nTiles + 2));
-    HIPCHK(hipMemsetAsync((uint32_t *)full->puTileCnt.p + nTiles, 0, 8, ctx->stream));
-    CandidateArgs A; A.L = trackLayout(T); A.pu = T.data.as<uint32_t>(); A.nSlots = nSlots; A.nTiles = nTiles;
-    A.bases = full->dBases.as<uint8_t>(); A.nBaseBytes = full->dBases.cap;
-    A.cnt = full->puTileCnt.as<uint32_t>(); A.start = full->puTileStart.as<uint32_t>(); A.out = nullptr; A.cap = 0;
-    const dim3 grid(gridFor((uint64_t)nTiles * 64, 256));
-    KL(k_pileup_count, grid, dim3(256), 0, ctx->stream, A);
-    rc = cubScan(ctx, full->puTileCnt.as<uint32_t>(), full->puTileStart.as<uint32_t>(), nTiles + 1); if (rc) return rc;
-    uint32_t tot = 0, scanFail = 0;
-    { const FetchPiece pc[2] = {{full->puTileStart.as<uint32_t>() + nTiles, &tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1}};
-      rc = fetchMany(ctx, pc, 2); if (rc) return rc; }
-    if (scanFail) return scanGaveUp(ctx, "pileup candidates");
+    CandidateSel A; A.L = trackLayout(T); A.pu = T.data.as<uint32_t>(); A.nSlots = (uint32_t)T.nBins; A.bases = full->dBases.as<uint8_t>(); A.nBaseBytes = full->dBases.cap;
+    A.out = nullptr;
+    TileSel t; uint32_t tot = 0;
+    rc = selectCount(full, TILES_PILEUP, A, T.nBins, "pileup candidates", &t, &tot); if (rc) return rc;
     ENSURE(full->puCand, 4ull * ((uint64_t)tot + 1));
-    A.out = full->puCand.as<uint32_t>(); A.cap = tot;
-    if (tot) KL(k_pileup_emit, grid, dim3(256), 0, ctx->stream, A);
+    A.out = full->puCand.as<uint32_t>(); t.cap = tot;
+    if (tot) KL(k_select_emit<CandidateSel>, selectGrid(t), dim3(256), 0, ctx->stream, A, t);
     HIPCHK(streamSync(ctx));
-    tlsPfFailed = nullptr;
     full->puNCand = tot; full->puHaveCand = true; *n = tot;
-    return 0;
+    return pfLeave();
 }
 int ygpu_pileup_candidates_collect(ygpu_ctx *full, uint32_t *slots)
 {
     if (!full || !full->stream) return YGPU_EINVAL;
-    if (!full->puHaveCand) { full->err = "ygpu_pileup_candidates_collect: ygpu_pileup_candidates_size has not been called on this context"; return YGPU_EINVAL; }
-    if (!full->puNCand) return 0;
-    if (!slots) return YGPU_EINVAL;
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
-    HIPCHK(hipSetDevice(full->device));
-    HIPCHK(hipMemcpyAsync(slots, full->puCand.p, 4ull * full->puNCand, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
-    tlsPfFailed = nullptr;
-    return 0;
+    return collectRecords(full, full->puHaveCand, "ygpu_pileup_candidates_collect: ygpu_pileup_candidates_size has not been called on this context", full->puNCand, slots,
+        full->puCand, 4);
 }
-// rows[i][ch] of the image's array for a caller's slots, a piece of the list at a time (the list and its rows pass through buffers of the context)
-int ygpu_pileup_gather(ygpu_ctx *full, const uint32_t *slots, uint64_t n, uint32_t *rows)
+// Rows of the image's array for a caller's slots, a piece of the list at a time (the list and its rows pass through buffers of the context): read into rows[i][ch]
+// (the gather), or -- a source folded into the array: the host's blocks, another image's rows -- added from them with global atomics (snv_stage.h k_pileup_add).
+static int pileupRows(ygpu_ctx *full, const char *who, const uint32_t *slots, uint32_t *rows, uint64_t n, bool add)
 {
     if (!full || !full->stream || (n && (!slots || !rows))) return YGPU_EINVAL;
-    if (!full->track[TRACK_PILEUP]) { full->err = "ygpu_pileup_gather: ygpu_pileup_enable has not been called on this context"; return YGPU_EINVAL; }
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
+    if (!full->track[TRACK_PILEUP]) return pfArgError(full, std::string(who) + ": ygpu_pileup_enable has not been called on this context");
+    PfSide *ctx = pfEnter(full);
     HIPCHK(hipSetDevice(full->device));
     HIPCHK(hipDeviceSynchronize());
     const TrackImage &T = *full->track[TRACK_PILEUP];
     const uint64_t piece = 1ull << 22;
     for (uint64_t at = 0; at < n; at += piece) {
-        const uint32_t m = (uint32_t)std::min<uint64_t>(piece, n - at);
+        const uint32_t m = (uint32_t)std::min<uint64_t>(piece, n - at); const dim3 grid(gridFor((uint64_t)m * ypileup::NCH, 256));
         ENSURE(full->puSlots, 4ull * m); ENSURE(full->puRows, 4ull * ypileup::NCH * m);
         HIPCHK(hipMemcpyAsync(full->puSlots.p, slots + at, 4ull * m, hipMemcpyHostToDevice, ctx->stream));
-        KL(k_pileup_gather, dim3(gridFor((uint64_t)m * ypileup::NCH, 256)), dim3(256), 0, ctx->stream, T.data.as<uint32_t>(), (uint32_t)T.nBins,
-            full->puSlots.as<uint32_t>(), m, full->puRows.as<uint32_t>());
-        HIPCHK(hipMemcpyAsync(rows + at * ypileup::NCH, full->puRows.p, 4ull * ypileup::NCH * m, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(streamSync(ctx));
-    }
-    tlsPfFailed = nullptr;
-    return 0;
-}
-// ---- SNV calls from the pileup array (snv_stage.h; the contract is in ../snv_core.h) -----------------------------------------------------------------------------
-// A source folded into the image's array: the caller's list and rows, a piece at a time through the gather's buffers, added with global atomics
-int ygpu_pileup_add(ygpu_ctx *full, const uint32_t *slots, const uint32_t *rows, uint64_t n)
-{
-    if (!full || !full->stream || (n && (!slots || !rows))) return YGPU_EINVAL;
-    if (!full->track[TRACK_PILEUP]) { full->err = "ygpu_pileup_add: ygpu_pileup_enable has not been called on this context"; return YGPU_EINVAL; }
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
-    HIPCHK(hipSetDevice(full->device));
-    HIPCHK(hipDeviceSynchronize());
-    const TrackImage &T = *full->track[TRACK_PILEUP];
-    const uint64_t piece = 1ull << 22;
-    for (uint64_t at = 0; at < n; at += piece) {
-        const uint32_t m = (uint32_t)std::min<uint64_t>(piece, n - at);
-        ENSURE(full->puSlots, 4ull * m); ENSURE(full->puRows, 4ull * ypileup::NCH * m);
-        HIPCHK(hipMemcpyAsync(full->puSlots.p, slots + at, 4ull * m, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(full->puRows.p, rows + at * ypileup::NCH, 4ull * ypileup::NCH * m, hipMemcpyHostToDevice, ctx->stream));
-        KL(k_pileup_add, dim3(gridFor((uint64_t)m * ypileup::NCH, 256)), dim3(256), 0, ctx->stream, T.data.as<uint32_t>(), (uint32_t)T.nBins,
-            full->puSlots.as<uint32_t>(), full->puRows.as<uint32_t>(), m);
+        if (add) {
+            HIPCHK(hipMemcpyAsync(full->puRows.p, rows + at * ypileup::NCH, 4ull * ypileup::NCH * m, hipMemcpyHostToDevice, ctx->stream));
+            KL(k_pileup_add, grid, dim3(256), 0, ctx->stream, T.data.as<uint32_t>(), (uint32_t)T.nBins, full->puSlots.as<uint32_t>(), full->puRows.as<uint32_t>(), m);
+        } else {
+            KL(k_pileup_gather, grid, dim3(256), 0, ctx->stream, T.data.as<uint32_t>(), (uint32_t)T.nBins, full->puSlots.as<uint32_t>(), m, full->puRows.as<uint32_t>());
+            HIPCHK(hipMemcpyAsync(rows + at * ypileup::NCH, full->puRows.p, 4ull * ypileup::NCH * m, hipMemcpyDeviceToHost, ctx->stream));
+        }
         HIPCHK(streamSync(ctx));                                               // (the caller's memory is pageable: the next piece may overwrite the buffers only now)
     }
-    tlsPfFailed = nullptr;
-    return 0;
+    return pfLeave();
 }
-// The calls of the image's array as it stands, ascending -- the candidates' three steps (count a tile, exclusive sums, emit) with the verdict of snv_core.h in the
-// place of the site test; the tiles' counts and sums live in the candidates' buffers (a selection of either kind leaves the other's RESULT alone).
+int ygpu_pileup_gather(ygpu_ctx *full, const uint32_t *slots, uint64_t n, uint32_t *rows) { return pileupRows(full, "ygpu_pileup_gather", slots, rows, n, false); }
+// ---- SNV calls from the pileup array (snv_stage.h; the contract is in ../snv_core.h) -----------------------------------------------------------------------------
+int ygpu_pileup_add(ygpu_ctx *full, const uint32_t *slots, const uint32_t *rows, uint64_t n)
+{
+    return pileupRows(full, "ygpu_pileup_add", slots, const_cast<uint32_t *>(rows), n, true);
+}
+// The calls of the image's array as it stands, ascending -- the candidates' steps with the verdict of snv_core.h in the place of the site test; the tiles'
+// counts and sums live in the candidates' buffers (a selection of either kind leaves the other's RESULT alone).
 int ygpu_snv_call_size(ygpu_ctx *full, const ygpu_snv_params *p, uint64_t *n)
 {
     if (!full || !full->stream || !p || !n) return YGPU_EINVAL;
-    if (!full->track[TRACK_PILEUP]) { full->err = "ygpu_snv_call_size: ygpu_pileup_enable has not been called on this context"; return YGPU_EINVAL; }
-    if (p->min_alt < 1 || p->min_depth < 1) { full->err = "ygpu_snv_call_size: min_alt and min_depth must be at least 1"; return YGPU_EINVAL; }
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
+    if (!full->track[TRACK_PILEUP]) return pfArgError(full, "ygpu_snv_call_size: ygpu_pileup_enable has not been called on this context");
+    if (p->min_alt < 1 || p->min_depth < 1) return pfArgError(full, "ygpu_snv_call_size: min_alt and min_depth must be at least 1");
+    PfSide *ctx = pfEnter(full);
     HIPCHK(hipSetDevice(full->device));
     HIPCHK(hipDeviceSynchronize());
     const TrackImage &T = *full->track[TRACK_PILEUP];
     full->snvHave = false; full->snvN = 0;
     int rc = pileupSide(full); if (rc) return rc;
-    const uint32_t nSlots = (uint32_t)T.nBins, nTiles = (uint32_t)((T.nBins + YS_TILE - 1) / YS_TILE);
-    ENSURE(full->puTileCnt, 4ull * (nTiles + 2)); ENSURE(full->puTileStart, 4ull * (nTiles + 2));
-    HIPCHK(hipMemsetAsync((uint32_t *)full->puTileCnt.p + nTiles, 0, 8, ctx->stream));
-    SnvArgs A; A.L = trackLayout(T); A.pu = T.data.as<uint32_t>(); A.nSlots = nSlots; A.nTiles = nTiles;
-    A.bases = full->dBases.as<uint8_t>(); A.nBaseBytes = full->dBases.cap; A.P = *p;
-    A.cnt = full->puTileCnt.as<uint32_t>(); A.start = full->puTileStart.as<uint32_t>(); A.out = nullptr; A.cap = 0;
-    const dim3 grid(gridFor((uint64_t)nTiles * 64, 256));
-    KL(k_snv_count, grid, dim3(256), 0, ctx->stream, A);
-    rc = cubScan(ctx, full->puTileCnt.as<uint32_t>(), full->puTileStart.as<uint32_t>(), nTiles + 1); if (rc) return rc;
-    uint32_t tot = 0, scanFail = 0;
-    { const FetchPiece pc[2] = {{full->puTileStart.as<uint32_t>() + nTiles, &tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1}};
-      rc = fetchMany(ctx, pc, 2); if (rc) return rc; }
-    if (scanFail) return scanGaveUp(ctx, "SNV calls");
+    SnvSel A; A.L = trackLayout(T); A.pu = T.data.as<uint32_t>(); A.nSlots = (uint32_t)T.nBins; A.bases = full->dBases.as<uint8_t>(); A.nBaseBytes = full->dBases.cap;
+    A.P = *p; A.out = nullptr;
+    TileSel t; uint32_t tot = 0;
+    rc = selectCount(full, TILES_PILEUP, A, T.nBins, "SNV calls", &t, &tot); if (rc) return rc;
     ENSURE(full->snvOut, sizeof(ygpu_snv_call) * ((uint64_t)tot + 1));
-    A.out = full->snvOut.as<ygpu_snv_call>(); A.cap = tot;
-    if (tot) KL(k_snv_emit, grid, dim3(256), 0, ctx->stream, A);
+    A.out = full->snvOut.as<ygpu_snv_call>(); t.cap = tot;
+    if (tot) KL(k_select_emit<SnvSel>, selectGrid(t), dim3(256), 0, ctx->stream, A, t);
     HIPCHK(streamSync(ctx));
-    tlsPfFailed = nullptr;
     full->snvN = tot; full->snvHave = true; *n = tot;
-    return 0;
+    return pfLeave();
 }
 int ygpu_snv_collect(ygpu_ctx *full, ygpu_snv_call *calls)
 {
     if (!full || !full->stream) return YGPU_EINVAL;
-    if (!full->snvHave || !full->snvOut.p) { full->err = "ygpu_snv_collect: ygpu_snv_call_size has not been called on this context"; return YGPU_EINVAL; }
-    if (!full->snvN) return 0;
-    if (!calls) return YGPU_EINVAL;
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
-    HIPCHK(hipSetDevice(full->device));
-    HIPCHK(hipMemcpyAsync(calls, full->snvOut.p, sizeof(ygpu_snv_call) * full->snvN, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
-    tlsPfFailed = nullptr;
-    return 0;
+    return collectRecords(full, full->snvHave && full->snvOut.p, "ygpu_snv_collect: ygpu_snv_call_size has not been called on this context", full->snvN, calls,
+        full->snvOut, sizeof(ygpu_snv_call));
 }
 // ---- indel alleles (indel_stage.h; the contract is in ../indel_core.h) -------------------------------------------------------------------------------------------
 // Per context, as the junctions are: a hash table of the context's own, fed by every ygpu_postfilter, drained by ygpu_indels_collect.
 int ygpu_indels_enable(ygpu_ctx *full, const ygpu_indel_params *p)
 {
     if (!full || !full->stream || !p) return YGPU_EINVAL;
-    tlsPfFailed = nullptr;
-    if (!full->oqSet) { full->err = "ygpu_indels_enable: ygpu_set_postfilter has not been called on this context (the alleles are counted behind the post-filter)";
-        return YGPU_EINVAL; }
-    if (!p->n_seqs || !p->seq_start || !p->seq_length || p->min_mapq > 255 || p->min_length < 1) {
-        full->err = "ygpu_indels_enable: bad mapping quality, minimum length or sequence table"; return YGPU_EINVAL; }
-    if (p->capacity && ((p->capacity & (p->capacity - 1)) != 0 || p->capacity > (1ull << 31))) {
-        full->err = "ygpu_indels_enable: the capacity must be a power of two of at most 2^31 entries (0: twice the batch capacity in bases)"; return YGPU_EINVAL; }
-    if (full->parked) { full->err = "ygpu_indels_enable: the context was parked (ygpu_park)"; return YGPU_EINVAL; }
+    if (!full->oqSet) return pfArgError(full, "ygpu_indels_enable: ygpu_set_postfilter has not been called on this context (the alleles are counted behind the post-filter)");
+    if (!p->n_seqs || !p->seq_start || !p->seq_length || p->min_mapq > 255 || p->min_length < 1)
+        return pfArgError(full, "ygpu_indels_enable: bad mapping quality, minimum length or sequence table");
+    if (p->capacity && ((p->capacity & (p->capacity - 1)) != 0 || p->capacity > (1ull << 31)))
+        return pfArgError(full, "ygpu_indels_enable: the capacity must be a power of two of at most 2^31 entries (0: twice the batch capacity in bases)");
+    if (full->parked) return pfArgError(full, "ygpu_indels_enable: the context was parked (ygpu_park)");
     std::vector<uint32_t> binBase(p->n_seqs + 1); uint64_t nSlots = 0;
-    if (!ydepth::layoutBins(p->seq_length, p->n_seqs, 1, binBase.data(), &nSlots) || nSlots == 0) { full->err = "ygpu_indels_enable: the slots do not fit 32 bits";
-        return YGPU_EINVAL; }
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
+    if (!ydepth::layoutBins(p->seq_length, p->n_seqs, 1, binBase.data(), &nSlots) || nSlots == 0) return pfArgError(full, "ygpu_indels_enable: the slots do not fit 32 bits");
+    PfSide *ctx = pfEnter(full);
     HIPCHK(hipSetDevice(full->device));
     HIPCHK(streamSync(ctx));                                                   // (a second enable: nothing of this side may still be using the table)
     ENSURE(full->idSeqStart, 4ull * p->n_seqs); ENSURE(full->idSeqLen, 4ull * p->n_seqs); ENSURE(full->idBinBase, 4ull * (p->n_seqs + 1)); ENSURE(full->idStats, 128);
@@ -585,9 +577,8 @@ int ygpu_indels_enable(ygpu_ctx *full, const ygpu_indel_params *p)
     HIPCHK(hipMemcpyAsync(full->idSeqLen.p, p->seq_length, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(full->idBinBase.p, binBase.data(), 4ull * (p->n_seqs + 1), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(streamSync(ctx));
-    tlsPfFailed = nullptr;
     full->idMinMapq = p->min_mapq; full->idMinLen = p->min_length; full->idNSeqs = p->n_seqs; full->idAuto = p->capacity == 0; full->idSet = true;
-    return 0;
+    return pfLeave();
 }
 int ygpu_indels_size(ygpu_ctx *ctx, uint64_t *used)
 {
@@ -598,68 +589,51 @@ int ygpu_indels_size(ygpu_ctx *ctx, uint64_t *used)
 int ygpu_indels_collect(ygpu_ctx *full, ygpu_indel_entry *out, uint64_t stats[6])
 {
     if (!full || !full->stream) return YGPU_EINVAL;
-    tlsPfFailed = nullptr;
-    if (!full->idSet) { full->err = "ygpu_indels_collect: ygpu_indels_enable has not been called on this context"; return YGPU_EINVAL; }
+    if (!full->idSet) return pfArgError(full, "ygpu_indels_collect: ygpu_indels_enable has not been called on this context");
+    pfLeave();                                                                 // (an earlier call's failure is not this call's: the returns below leave no name behind)
     if (stats) for (int k = 0; k < 6; k++) stats[k] = 0;
     if (!full->idTable.p) return 0;                                            // (parked: the table went with the arenas)
     if (full->idUsed && !out) return YGPU_EINVAL;
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
+    PfSide *ctx = pfEnter(full);
     HIPCHK(hipSetDevice(full->device));
     int rc = pileupSide(full); if (rc) return rc;
-    const uint32_t nTiles = (uint32_t)((full->idCap + YI_TILE - 1) / YI_TILE);
-    ENSURE(full->idTileCnt, 4ull * (nTiles + 2)); ENSURE(full->idTileStart, 4ull * (nTiles + 2));
-    HIPCHK(hipMemsetAsync((uint32_t *)full->idTileCnt.p + nTiles, 0, 8, ctx->stream));
-    IndelDrainArgs A; A.table = full->idTable.as<ygpu_indel_entry>(); A.capacity = full->idCap; A.nTiles = nTiles; A.cnt = full->idTileCnt.as<uint32_t>();
-    A.start = full->idTileStart.as<uint32_t>(); A.out = nullptr; A.cap = 0;
-    const dim3 grid(gridFor((uint64_t)nTiles * 64, 256));
-    KL(k_indel_count, grid, dim3(256), 0, ctx->stream, A);
-    rc = cubScan(ctx, full->idTileCnt.as<uint32_t>(), full->idTileStart.as<uint32_t>(), nTiles + 1); if (rc) return rc;
-    uint32_t tot = 0, scanFail = 0; unsigned long long h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    { const FetchPiece pc[3] = {{full->idTileStart.as<uint32_t>() + nTiles, &tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1},
-        {full->idStats.p, (uint32_t *)h, 18}}; rc = fetchMany(ctx, pc, 3); if (rc) return rc; }
-    if (scanFail) return scanGaveUp(ctx, "indel alleles");
+    IndelDrainSel A; A.table = full->idTable.as<ygpu_indel_entry>(); A.capacity = full->idCap; A.out = nullptr;
+    TileSel t; uint32_t tot = 0; unsigned long long h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    rc = selectCount(full, TILES_INDEL, A, full->idCap, "indel alleles", &t, &tot, {full->idStats.p, (uint32_t *)h, 18}); if (rc) return rc;
     // (the caller sized `out` by ygpu_indels_size: after a ygpu_postfilter that failed half-way the two may differ -- the size is put right, the call fails)
     if (tot != full->idUsed) { char m[200]; snprintf(m, sizeof m, "ygpu_indels_collect: %u occupied entries, ygpu_indels_size said %u (it now says %u: collect again)", tot,
         full->idUsed, tot); ctx->err = m; full->idUsed = tot; return YGPU_EINTERNAL; }
     if (tot) {
         ENSURE(full->idOut, sizeof(ygpu_indel_entry) * (uint64_t)tot);
-        A.out = full->idOut.as<ygpu_indel_entry>(); A.cap = tot;
-        KL(k_indel_emit, grid, dim3(256), 0, ctx->stream, A);
+        A.out = full->idOut.as<ygpu_indel_entry>(); t.cap = tot;
+        KL(k_select_emit<IndelDrainSel>, selectGrid(t), dim3(256), 0, ctx->stream, A, t);
         HIPCHK(hipMemcpyAsync(out, full->idOut.p, sizeof(ygpu_indel_entry) * (uint64_t)tot, hipMemcpyDeviceToHost, ctx->stream));
     }
     // ... and the table, its statistics and the two words are clean for the next batch
     HIPCHK(hipMemsetAsync(full->idTable.p, 0, sizeof(ygpu_indel_entry) * full->idCap, ctx->stream));
     HIPCHK(hipMemsetAsync(full->idStats.p, 0, 128, ctx->stream));
     HIPCHK(streamSync(ctx));
-    tlsPfFailed = nullptr;
     full->idUsed = 0;
     if (stats) { for (int k = 0; k < 5; k++) stats[k] = h[k]; stats[5] = (uint32_t)(h[8] >> 32); }
-    return 0;
+    return pfLeave();
 }
 // ---- indel calls (indelcall_stage.h; the contract is in ../indelcall_core.h) --------------------------------------------------------------------------------------
 // The raw alleles normalised against the image's reference and merged in a table of the context's own, made (and cleared) for the call; the layout is the
 // pileup's.  On the post-filter's side of the context, once everything queued on the device has finished; serves a parked context as the SNV calls do.
-static bool indelEntryLess(const ygpu_indel_entry &a, const ygpu_indel_entry &b)
-{
-    return yindel::keyLess(yindel::Key{a.w0, a.w1, a.w2}, yindel::Key{b.w0, b.w1, b.w2});
-}
+static const auto indelKeyLess = [](const auto &a, const auto &b) { return yindel::keyLess(yindel::Key{a.w0, a.w1, a.w2}, yindel::Key{b.w0, b.w1, b.w2}); };
 int ygpu_indelcall_normalize(ygpu_ctx *full, const ygpu_indel_entry *raw, uint64_t n, uint32_t max_shift, uint64_t *n_out, uint64_t stats[4])
 {
     if (!full || !full->stream || !n_out || (n && !raw)) return YGPU_EINVAL;
-    if (!full->track[TRACK_PILEUP]) { full->err = "ygpu_indelcall_normalize: ygpu_pileup_enable has not been called on this context (the layout is the pileup's)";
-        return YGPU_EINVAL; }
-    if (max_shift > (uint32_t)yindelcall::MAX_SHIFT || n > (1ull << 30)) { full->err = "ygpu_indelcall_normalize: max_shift must be at most 65535, n at most 2^30";
-        return YGPU_EINVAL; }
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
+    if (!full->track[TRACK_PILEUP]) return pfArgError(full, "ygpu_indelcall_normalize: ygpu_pileup_enable has not been called on this context (the layout is the pileup's)");
+    if (max_shift > (uint32_t)yindelcall::MAX_SHIFT || n > (1ull << 30)) return pfArgError(full, "ygpu_indelcall_normalize: max_shift must be at most 65535, n at most 2^30");
+    PfSide *ctx = pfEnter(full);
     HIPCHK(hipSetDevice(full->device));
     HIPCHK(hipDeviceSynchronize());
     const TrackImage &T = *full->track[TRACK_PILEUP];
     full->icHave = full->icHaveCalls = false; full->icN = full->icCalls = 0;
     if (stats) { stats[0] = n; stats[1] = stats[2] = stats[3] = 0; }
     *n_out = 0;
-    if (n == 0) { tlsPfFailed = nullptr; full->icHave = true; return 0; }
+    if (n == 0) { full->icHave = true; return pfLeave(); }
     int rc = pileupSide(full); if (rc) return rc;
     uint64_t capacity = 1024; while (capacity < 2 * n) capacity <<= 1;
     ENSURE(full->icRaw, sizeof(ygpu_indel_entry) * n); ENSURE(full->icTable, sizeof(ygpu_indel_entry) * capacity); ENSURE(full->icStats, 64);
@@ -671,108 +645,71 @@ int ygpu_indelcall_normalize(ygpu_ctx *full, const ygpu_indel_entry *raw, uint64
     N.raw = full->icRaw.as<ygpu_indel_entry>(); N.n = (uint32_t)n; N.maxShift = max_shift; N.table = full->icTable.as<ygpu_indel_entry>(); N.mask = (uint32_t)(capacity - 1);
     N.stats = full->icStats.as<unsigned long long>(); N.used = full->icStats.as<uint32_t>() + 8;
     KL(k_indel_norm, dim3(gridFor(n * 64, 256)), dim3(256), 0, ctx->stream, N);
-    // the table's occupied entries, compacted: the indel table's count and sums, the emit that saturates
-    const uint32_t nTiles = (uint32_t)((capacity + YI_TILE - 1) / YI_TILE);
-    ENSURE(full->idTileCnt, 4ull * (nTiles + 2)); ENSURE(full->idTileStart, 4ull * (nTiles + 2));
-    HIPCHK(hipMemsetAsync((uint32_t *)full->idTileCnt.p + nTiles, 0, 8, ctx->stream));
-    IndelDrainArgs A; A.table = full->icTable.as<ygpu_indel_entry>(); A.capacity = capacity; A.nTiles = nTiles; A.cnt = full->idTileCnt.as<uint32_t>();
-    A.start = full->idTileStart.as<uint32_t>(); A.out = nullptr; A.cap = 0;
-    const dim3 grid(gridFor((uint64_t)nTiles * 64, 256));
-    KL(k_indel_count, grid, dim3(256), 0, ctx->stream, A);
-    rc = cubScan(ctx, full->idTileCnt.as<uint32_t>(), full->idTileStart.as<uint32_t>(), nTiles + 1); if (rc) return rc;
-    uint32_t tot = 0, scanFail = 0; unsigned long long h[4] = {0, 0, 0, 0};
-    { const FetchPiece pc[3] = {{full->idTileStart.as<uint32_t>() + nTiles, &tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1},
-        {full->icStats.p, (uint32_t *)h, 8}}; rc = fetchMany(ctx, pc, 3); if (rc) return rc; }
-    if (scanFail) return scanGaveUp(ctx, "indel calls");
+    // the table's occupied entries, compacted: the indel table's pick, the store that saturates
+    IndelMergeDrainSel A; A.table = full->icTable.as<ygpu_indel_entry>(); A.capacity = capacity; A.out = nullptr;
+    TileSel t; uint32_t tot = 0; unsigned long long h[4] = {0, 0, 0, 0};
+    rc = selectCount<IndelDrainSel>(full, TILES_INDEL, A, capacity, "indel calls", &t, &tot, {full->icStats.p, (uint32_t *)h, 8}); if (rc) return rc;      // (the pick is shared)
     if (h[2]) { ctx->err = "ygpu_indelcall_normalize: a normalised allele found no entry in the merge table"; return YGPU_EINTERNAL; }
     if (tot) {
         ENSURE(full->icAlleles, sizeof(ygpu_indel_entry) * (uint64_t)tot);
-        A.out = full->icAlleles.as<ygpu_indel_entry>(); A.cap = tot;
-        KL(k_indelcall_drain, grid, dim3(256), 0, ctx->stream, A);
+        A.out = full->icAlleles.as<ygpu_indel_entry>(); t.cap = tot;
+        KL(k_select_emit<IndelMergeDrainSel>, selectGrid(t), dim3(256), 0, ctx->stream, A, t);
     }
     HIPCHK(streamSync(ctx));
-    tlsPfFailed = nullptr;
     full->icN = tot; full->icHave = true; *n_out = tot;
     if (stats) { stats[1] = h[0]; stats[3] = h[1]; stats[2] = n - h[1] - tot; }
-    return 0;
+    return pfLeave();
 }
 int ygpu_indelcall_alleles(ygpu_ctx *full, ygpu_indel_entry *out)
 {
     if (!full || !full->stream) return YGPU_EINVAL;
-    if (!full->icHave) { full->err = "ygpu_indelcall_alleles: ygpu_indelcall_normalize has not been called on this context"; return YGPU_EINVAL; }
-    if (!full->icN) return 0;
-    if (!out || !full->icAlleles.p) return YGPU_EINVAL;
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
-    HIPCHK(hipSetDevice(full->device));
-    HIPCHK(hipMemcpyAsync(out, full->icAlleles.p, sizeof(ygpu_indel_entry) * full->icN, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
-    tlsPfFailed = nullptr;
-    std::sort(out, out + full->icN, indelEntryLess);                           // (the table keeps no order: see the header)
-    return 0;
+    const int rc = collectRecords(full, full->icHave, "ygpu_indelcall_alleles: ygpu_indelcall_normalize has not been called on this context", full->icN, out,
+        full->icAlleles, sizeof(ygpu_indel_entry));
+    if (rc == 0 && full->icN) std::sort(out, out + full->icN, indelKeyLess);      // (the table keeps no order: see the header)
+    return rc;
 }
-// The calls among the merged alleles against the image's array as it stands: count a tile, exclusive sums, emit -- the SNV calls' three steps, a lane an allele.
+// The calls among the merged alleles against the image's array as it stands: the SNV calls' steps, a lane an allele.
 int ygpu_indelcall_size(ygpu_ctx *full, const ygpu_indelcall_params *p, uint64_t *n)
 {
     if (!full || !full->stream || !p || !n) return YGPU_EINVAL;
-    if (!full->track[TRACK_PILEUP]) { full->err = "ygpu_indelcall_size: ygpu_pileup_enable has not been called on this context"; return YGPU_EINVAL; }
-    if (!full->icHave) { full->err = "ygpu_indelcall_size: ygpu_indelcall_normalize has not been called on this context"; return YGPU_EINVAL; }
-    if (p->min_alt < 1 || p->min_depth < 1) { full->err = "ygpu_indelcall_size: min_alt and min_depth must be at least 1"; return YGPU_EINVAL; }
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
+    if (!full->track[TRACK_PILEUP]) return pfArgError(full, "ygpu_indelcall_size: ygpu_pileup_enable has not been called on this context");
+    if (!full->icHave) return pfArgError(full, "ygpu_indelcall_size: ygpu_indelcall_normalize has not been called on this context");
+    if (p->min_alt < 1 || p->min_depth < 1) return pfArgError(full, "ygpu_indelcall_size: min_alt and min_depth must be at least 1");
+    PfSide *ctx = pfEnter(full);
     HIPCHK(hipSetDevice(full->device));
     HIPCHK(hipDeviceSynchronize());
     full->icHaveCalls = false; full->icCalls = 0; *n = 0;
-    if (!full->icN || !full->icAlleles.p) { tlsPfFailed = nullptr; full->icHaveCalls = true; return 0; }
+    if (!full->icN || !full->icAlleles.p) { full->icHaveCalls = true; return pfLeave(); }
     const TrackImage &T = *full->track[TRACK_PILEUP];
     int rc = pileupSide(full); if (rc) return rc;
-    const uint32_t nAl = (uint32_t)full->icN, nTiles = (nAl + YC_TILE - 1) / YC_TILE;
-    ENSURE(full->idTileCnt, 4ull * (nTiles + 2)); ENSURE(full->idTileStart, 4ull * (nTiles + 2));
-    HIPCHK(hipMemsetAsync((uint32_t *)full->idTileCnt.p + nTiles, 0, 8, ctx->stream));
-    IndelCallArgs A; A.L = trackLayout(T); A.pu = T.data.as<uint32_t>(); A.nSlots = (uint32_t)T.nBins; A.bases = full->dBases.as<uint8_t>(); A.nBaseBytes = full->dBases.cap;
-    A.alleles = full->icAlleles.as<ygpu_indel_entry>(); A.n = nAl; A.nTiles = nTiles; A.P = *p;
-    A.cnt = full->idTileCnt.as<uint32_t>(); A.start = full->idTileStart.as<uint32_t>(); A.out = nullptr; A.cap = 0;
-    const dim3 grid(gridFor((uint64_t)nTiles * 64, 256));
-    KL(k_indelcall_count, grid, dim3(256), 0, ctx->stream, A);
-    rc = cubScan(ctx, full->idTileCnt.as<uint32_t>(), full->idTileStart.as<uint32_t>(), nTiles + 1); if (rc) return rc;
-    uint32_t tot = 0, scanFail = 0;
-    { const FetchPiece pc[2] = {{full->idTileStart.as<uint32_t>() + nTiles, &tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1}};
-      rc = fetchMany(ctx, pc, 2); if (rc) return rc; }
-    if (scanFail) return scanGaveUp(ctx, "indel calls");
+    IndelCallSel A; A.L = trackLayout(T); A.pu = T.data.as<uint32_t>(); A.nSlots = (uint32_t)T.nBins; A.bases = full->dBases.as<uint8_t>(); A.nBaseBytes = full->dBases.cap;
+    A.alleles = full->icAlleles.as<ygpu_indel_entry>(); A.n = (uint32_t)full->icN; A.P = *p; A.out = nullptr;
+    TileSel t; uint32_t tot = 0;
+    rc = selectCount(full, TILES_INDEL, A, A.n, "indel calls", &t, &tot); if (rc) return rc;
     ENSURE(full->icOut, sizeof(ygpu_indel_call) * ((uint64_t)tot + 1));
-    A.out = full->icOut.as<ygpu_indel_call>(); A.cap = tot;
-    if (tot) KL(k_indelcall_emit, grid, dim3(256), 0, ctx->stream, A);
+    A.out = full->icOut.as<ygpu_indel_call>(); t.cap = tot;
+    if (tot) KL(k_select_emit<IndelCallSel>, selectGrid(t), dim3(256), 0, ctx->stream, A, t);
     HIPCHK(streamSync(ctx));
-    tlsPfFailed = nullptr;
     full->icCalls = tot; full->icHaveCalls = true; *n = tot;
-    return 0;
+    return pfLeave();
 }
 int ygpu_indelcall_collect(ygpu_ctx *full, ygpu_indel_call *calls)
 {
     if (!full || !full->stream) return YGPU_EINVAL;
-    if (!full->icHaveCalls) { full->err = "ygpu_indelcall_collect: ygpu_indelcall_size has not been called on this context"; return YGPU_EINVAL; }
-    if (!full->icCalls) return 0;
-    if (!calls || !full->icOut.p) return YGPU_EINVAL;
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
-    HIPCHK(hipSetDevice(full->device));
-    HIPCHK(hipMemcpyAsync(calls, full->icOut.p, sizeof(ygpu_indel_call) * full->icCalls, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
-    tlsPfFailed = nullptr;
-    std::sort(calls, calls + full->icCalls, [](const ygpu_indel_call &a, const ygpu_indel_call &b) {
-        return yindel::keyLess(yindel::Key{a.w0, a.w1, a.w2}, yindel::Key{b.w0, b.w1, b.w2}); });
-    return 0;
+    const int rc = collectRecords(full, full->icHaveCalls, "ygpu_indelcall_collect: ygpu_indelcall_size has not been called on this context", full->icCalls, calls,
+        full->icOut, sizeof(ygpu_indel_call));
+    if (rc == 0 && full->icCalls) std::sort(calls, calls + full->icCalls, indelKeyLess);
+    return rc;
 }
 // ---- the error profile (eprofile_stage.h; the contract is in ../eprofile_core.h) ------------------------------------------------------------------------------
 // Per context, as the indel alleles are: a table of the context's own, fed by every ygpu_postfilter, read (not cleared) by ygpu_eprofile_collect.
 int ygpu_eprofile_enable(ygpu_ctx *full, const ygpu_eprofile_params *p)
 {
     if (!full || !full->stream || !p) return YGPU_EINVAL;
-    tlsPfFailed = nullptr;
-    if (!full->oqSet) { full->err = "ygpu_eprofile_enable: ygpu_set_postfilter has not been called on this context (the profile is counted behind the post-filter)";
-        return YGPU_EINVAL; }
-    if (!p->n_seqs || !p->seq_start || !p->seq_length || p->min_mapq > 255) { full->err = "ygpu_eprofile_enable: bad mapping quality or sequence table"; return YGPU_EINVAL; }
-    if (full->parked) { full->err = "ygpu_eprofile_enable: the context was parked (ygpu_park)"; return YGPU_EINVAL; }
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
+    if (!full->oqSet) return pfArgError(full, "ygpu_eprofile_enable: ygpu_set_postfilter has not been called on this context (the profile is counted behind the post-filter)");
+    if (!p->n_seqs || !p->seq_start || !p->seq_length || p->min_mapq > 255) return pfArgError(full, "ygpu_eprofile_enable: bad mapping quality or sequence table");
+    if (full->parked) return pfArgError(full, "ygpu_eprofile_enable: the context was parked (ygpu_park)");
+    PfSide *ctx = pfEnter(full);
     HIPCHK(hipSetDevice(full->device));
     HIPCHK(streamSync(ctx));                                                   // (a second enable: nothing of this side may still be using the table)
     full->epSet = false;
@@ -781,9 +718,8 @@ int ygpu_eprofile_enable(ygpu_ctx *full, const ygpu_eprofile_params *p)
     HIPCHK(hipMemcpyAsync(full->epSeqs.p, p->seq_start, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(full->epSeqs.as<uint32_t>() + p->n_seqs, p->seq_length, 4ull * p->n_seqs, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(streamSync(ctx));
-    tlsPfFailed = nullptr;
     full->epMinMapq = p->min_mapq; full->epNSeqs = p->n_seqs; full->epSet = true;
-    return 0;
+    return pfLeave();
 }
 int ygpu_eprofile_size(ygpu_ctx *ctx, uint64_t *n_words)
 {
@@ -795,19 +731,16 @@ int ygpu_eprofile_size(ygpu_ctx *ctx, uint64_t *n_words)
 int ygpu_eprofile_collect(ygpu_ctx *full, uint64_t *words, uint64_t stats[4])
 {
     if (!full || !full->stream) return YGPU_EINVAL;
-    tlsPfFailed = nullptr;
-    if (!full->epSet) { full->err = "ygpu_eprofile_collect: ygpu_eprofile_enable has not been called on this context"; return YGPU_EINVAL; }
+    if (!full->epSet) return pfArgError(full, "ygpu_eprofile_collect: ygpu_eprofile_enable has not been called on this context");
     unsigned long long h[YE_LDS_WORDS]; memset(h, 0, sizeof h);
     if (full->epTable.p) {                                                     // (parked: the table went with the arenas -- a parked context never ran a batch)
-        PfSide *ctx = &full->pf;
-        tlsPfFailed = full;
+        PfSide *ctx = pfEnter(full);
         HIPCHK(hipSetDevice(full->device));
         HIPCHK(hipMemcpyAsync(h, full->epTable.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(streamSync(ctx));
-        tlsPfFailed = nullptr;
     }
     if (words) for (uint32_t k = 0; k < (uint32_t)yeprofile::WORDS; k++) words[k] = h[k];
     if (stats) for (uint32_t k = 0; k < 4; k++) stats[k] = h[yeprofile::WORDS + k];
-    return 0;
+    return pfLeave();
 }
 // ---- split-read junctions (junction_stage.h; the contract is in ../junction_core.h) --------------------------------------------------------------------------
 // Per batch and per context, unlike the binned tracks above: the junctions of the batch the context's last ygpu_postfilter filtered.
@@ -828,18 +761,15 @@ int ygpu_junctions_enable(ygpu_ctx *ctx, const ygpu_junction_params *p)
 // the number of junctions of the filtered batch: the last word of the exclusive sums, fetched once (with the flag of a look-back that gave up)
 static int junctionsTotal(ygpu_ctx *full, const char *who)
 {
-    if (!full->jnSet) { full->err = std::string(who) + ": ygpu_junctions_enable has not been called on this context"; return YGPU_EINVAL; }
-    if (!full->jnDone) { full->err = std::string(who) + ": no ygpu_postfilter has run on this context since ygpu_junctions_enable"; return YGPU_EINVAL; }
+    if (!full->jnSet) return pfArgError(full, std::string(who) + ": ygpu_junctions_enable has not been called on this context");
+    if (!full->jnDone) return pfArgError(full, std::string(who) + ": no ygpu_postfilter has run on this context since ygpu_junctions_enable");
     if (full->jnHaveTotal) return 0;
     if (full->jnReads == 0) { full->jnTotal = 0; full->jnHaveTotal = true; return 0; }
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
+    PfSide *ctx = pfEnter(full);
     HIPCHK(hipSetDevice(full->device));
-    uint32_t tot = 0, scanFail = 0;
-    { const FetchPiece pc[2] = {{full->jnStart.as<uint32_t>() + full->jnReads, &tot, 1}, {ctx->counters.as<uint32_t>() + CNT_SCANFAIL, &scanFail, 1}};
-      const int rc = fetchMany(ctx, pc, 2); if (rc) return rc; }
-    if (scanFail) return scanGaveUp(ctx, "junctions");
-    tlsPfFailed = nullptr;
+    uint32_t tot = 0;
+    const int rc = fetchTotal(ctx, full->jnStart.as<uint32_t>() + full->jnReads, "junctions", &tot); if (rc) return rc;
+    pfLeave();
     if ((uint64_t)tot * sizeof(ygpu_junction) > full->jnOut.cap) { full->err = std::string(who) + ": more junctions than the batch has clumps"; return YGPU_EINTERNAL; }
     full->jnTotal = tot; full->jnHaveTotal = true;
     return 0;
@@ -856,16 +786,14 @@ int ygpu_junctions_collect(ygpu_ctx *full, ygpu_junction *out, uint64_t stats[4]
     const int rc = junctionsTotal(full, "ygpu_junctions_collect"); if (rc) return rc;
     if (stats) for (int k = 0; k < 4; k++) stats[k] = 0;
     if (full->jnReads == 0) return 0;
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
+    PfSide *ctx = pfEnter(full);
     HIPCHK(hipSetDevice(full->device));
     unsigned long long h[4] = {0, 0, 0, 0};
     if (out && full->jnTotal) HIPCHK(hipMemcpyAsync(out, full->jnOut.p, sizeof(ygpu_junction) * (uint64_t)full->jnTotal, hipMemcpyDeviceToHost, ctx->stream));
     if (stats) HIPCHK(hipMemcpyAsync(h, full->jnStats.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(streamSync(ctx));
-    tlsPfFailed = nullptr;
     if (stats) for (int k = 0; k < 4; k++) stats[k] = h[k];
-    return 0;
+    return pfLeave();
 }
 int ygpu_inject_results(ygpu_ctx *ctx, const ygpu_result_batch *r)
 {
@@ -897,19 +825,17 @@ int ygpu_filtered_size(ygpu_ctx *ctx, uint64_t *n_clumps, uint64_t *n_ops)
 int ygpu_collect_filtered(ygpu_ctx *full, uint32_t *clump_start, ygpu_out_clump *clumps, uint32_t *ops, ygpu_filtered_batch *out)
 {
     if (!full || !out || !clump_start || !full->oqDone || (full->nFOut && !clumps) || (full->nFOps && !ops)) return YGPU_EINVAL;
-    PfSide *ctx = &full->pf;
-    tlsPfFailed = full;
+    PfSide *ctx = pfEnter(full);
     HIPCHK(hipSetDevice(full->device));
     const uint32_t n = full->pfN;
     HIPCHK(hipMemcpyAsync(clump_start, full->oqOutStart.p, 4ull * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
     if (full->nFOut) HIPCHK(hipMemcpyAsync(clumps, full->oqFClumps.p, sizeof(ygpu_out_clump) * (uint64_t)full->nFOut, hipMemcpyDeviceToHost, ctx->stream));
     if (full->nFOps) HIPCHK(hipMemcpyAsync(ops, full->oqFOps.p, 4ull * full->nFOps, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(streamSync(ctx));
-    tlsPfFailed = nullptr;
     // (collected: a later ygpu_filtered_size without a new ygpu_postfilter is an error, not the previous batch once more)
     full->oqDone = false;
     out->n_reads = n; out->clump_start = clump_start; out->clumps = clumps; out->ops = ops; out->n_clumps = full->nFOut; out->n_ops = full->nFOps; out->counters = full->pfCounters;
-    return 0;
+    return pfLeave();
 }
 }  // extern "C"
 
