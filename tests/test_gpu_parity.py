@@ -431,7 +431,7 @@ def test_index_built_on_the_device_is_byte_identical(work, meta, tmp_path):
     g = os.path.join(d, "genome_small.nib2")
     for args, name in ((["-L", "11"], "genome_small.X11_01_65525S"), (["-L", "8", "-H", "20"], "genome_small.X08_01_00020S")):
         r = subprocess.run([ya.CLI_PATH, "-g", g] + args, stderr=subprocess.PIPE, check=True)
-        assert b"Building the index on GPU" in r.stderr
+        assert b"Building the index on GPU" in r.stderr and b"Index build on the GPU failed" not in r.stderr, r.stderr[-2000:]
         assert os.path.getsize(os.path.join(d, name)) == meta["index"][name]["size"] if "size" in meta["index"][name] else True
         assert _sha(os.path.join(d, name)) == meta["index"][name]["sha256"], name
     # a repeat-rich 6 Mbp genome: -L 15 (the default; 4.3 GB table), and -L 10 -H 40 where thousands of k-mers are sampled and the long lists take
@@ -440,7 +440,9 @@ def test_index_built_on_the_device_is_byte_identical(work, meta, tmp_path):
     subprocess.check_call([os.path.join(ROOT, "tools", "yaha_sim"), "genome", "--seed", "5", "--out", big, "--seqs", "5", "--len", "6000000", "--repeat-frac", "0.5", "--nrun", "3", "--lowcomplex", "6"])
     for args, name in ((["-L", "15"], "big.X15_01_65525S"), (["-L", "10", "-H", "40"], "big.X10_01_00040S"), (["-L", "12", "-H", "3000"], "big.X12_01_03000S"),
                        (["-L", "13", "-S", "2"], "big.X13_02_65525S"), (["-L", "11", "-S", "7", "-H", "100"], "big.X11_07_00100S"), (["-L", "12", "-S", "12"], "big.X12_12_65525S")):      # -S > 1: starts follow the reference's scan (N runs re-phase it)
-        subprocess.run([ya.CLI_PATH, "-g", big] + args, stderr=subprocess.DEVNULL, check=True)
+        r = subprocess.run([ya.CLI_PATH, "-g", big] + args, stderr=subprocess.PIPE, check=True)
+        # (runIndex falls back to the host builder when the device build fails: without these two the comparison below would be host against host)
+        assert b"Building the index on GPU" in r.stderr and b"Index build on the GPU failed" not in r.stderr, r.stderr[-2000:]
         dev = os.path.join(d, name + ".device")
         os.rename(os.path.join(d, name), dev)
         r = subprocess.run([ya.CLI_PATH, "-g", big, "-cpuindex"] + args, stderr=subprocess.PIPE, check=True)
@@ -451,7 +453,8 @@ def test_index_built_on_the_device_is_byte_identical(work, meta, tmp_path):
             # once more with the lists of more than 64 entries handed to the multi-workgroup sort (a bitonic network over padded copies, index_build.hip): what only the few
             # satellite k-mers of a 3 Gbp genome take otherwise (a list beyond 8 192 entries)
             os.rename(os.path.join(d, name), os.path.join(d, name + ".host"))
-            subprocess.run([ya.CLI_PATH, "-g", big] + args, stderr=subprocess.DEVNULL, check=True, env=dict(os.environ, YAHA_IX_HUGE_MIN="64"))
+            r = subprocess.run([ya.CLI_PATH, "-g", big] + args, stderr=subprocess.PIPE, check=True, env=dict(os.environ, YAHA_IX_HUGE_MIN="64"))
+            assert b"Building the index on GPU" in r.stderr and b"Index build on the GPU failed" not in r.stderr, r.stderr[-2000:]
             assert subprocess.run(["cmp", "-s", os.path.join(d, name + ".host"), os.path.join(d, name)]).returncode == 0, "device-built index (long lists through the multi-workgroup sort) differs from the host-built one: " + name
             os.remove(os.path.join(d, name + ".host"))
         os.remove(os.path.join(d, name))

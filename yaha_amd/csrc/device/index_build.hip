@@ -8,7 +8,8 @@
 //   k_ix_fill    the same walk; slot = startingOffs[h] + atomicAdd(cursor[h]) -- the order inside a k-mer's list is whatever the atomics gave
 //   k_ix_order*  every list is put into ascending offset order, which is the ONLY order the reference can produce (its fill pass scans the genome
 //                left to right, Index.c:201-229), so the result is independent of the atomics: lists of <= 32 entries are insertion-sorted by one
-//                thread (they arrive almost sorted), up to 8 192 entries by one workgroup in LDS (bitonic), longer ones by a device radix sort each
+//                thread (they arrive almost sorted), up to 8 192 entries by one workgroup in LDS (bitonic), longer ones by a multi-launch
+//                bitonic network over a padded copy each
 //   sampling     k-mers with more than maxHits occurrences keep a Floyd sample drawn with the default-seeded Marsaglia generator, consumed in
 //                k-mer order (Index.c:271-315, Math.c:304-343): inherently sequential, but it concerns a handful of k-mers -- their lists go to
 //                the host, the samples come back, and one gather pass compacts ROA (k_ix_compact).
@@ -275,6 +276,8 @@ bool buildIndexDevice(int device, const Genome &g, int wordLen, int skipDist, in
     lap("fill");
     // order every list
     uint32_t bigCap = 1u << 22, overCap = 1u << 20; unsigned int two[2] = {0, 0};
+    // (YAHA_IX_LIST_CAP: a test hook -- both arrays start with room for that many k-mers, so that a small genome overflows them and the regrow-and-redo below runs)
+    if (const char *e = getenv("YAHA_IX_LIST_CAP")) { const long v = atol(e); if (v >= 1 && v < (long)overCap) bigCap = overCap = (uint32_t)v; }
     IXCHK(hipMalloc(&dBig.p, 4ull * bigCap)); IXCHK(hipMalloc(&dOver.p, 4ull * overCap)); IXCHK(hipMalloc(&dN.p, 8));
     for (int attempt = 0;; attempt++) {
         IXCHK(hipMemset(dN.p, 0, 8));
@@ -352,7 +355,8 @@ bool buildIndexDevice(int device, const Genome &g, int wordLen, int skipDist, in
         std::sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return ov[4 * a] < ov[4 * b]; });
         // groups of lists of at most 64 M entries: pack on the device, one copy down, sample on the host in k-mer order (the generator is sequential by
         // definition), one copy of the samples up, scatter on the device
-        const uint64_t groupCap = 64ull << 20;
+        // (YAHA_IX_GROUP_CAP: a test hook -- that many entries a group instead, so that a small genome's lists go through several groups)
+        uint64_t groupCap = 64ull << 20; if (const char *e = getenv("YAHA_IX_GROUP_CAP")) { const long v = atol(e); if (v >= 1 && v < (long)groupCap) groupCap = (uint64_t)v; }
         std::vector<uint32_t> desc, dst, packed, samples; Buf dDesc, dDst, dPacked, dSamples;
         size_t g0 = 0;
         while (g0 < idx.size()) {

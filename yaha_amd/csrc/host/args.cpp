@@ -21,7 +21,7 @@ static void usage(FILE *o)
           "Index creation:\n"
           "  yaha -g genome.{fa|fna|fasta|nib2} [-H maxHits (65525)] [-L wordLen (15)] [-S skipDist (1)] [-device D (0)] [-cpuindex]\n"
           "  yaha -g genome.{fa|fna|fasta} -c   (compress to genome.nib2 only)      yaha -g genome.nib2 -u   (back to genome.fasta)\n"
-          "       (built on the GPU when one is visible and -S is 1; -cpuindex forces the host builder; the files are identical)\n\n"
+          "       (built on the GPU when one is visible, for any -S; -cpuindex forces the host builder; the files are identical)\n\n"
           "Query alignment (hot path on MI355X):\n"
           "  yaha -x indexFile [-q queryFile|(stdin)] [-o8|(-osh)|-oss|-obh|-obs outFile|(stdout)] [-obsort [-sortmem GB (32)]] [-t hostThreads (1)]\n"
           "       [-gpus N (1)] [-ctx contextsPerGpu (3)] [-device D (0)] [-batch readsPerBatch (about 16 M bases)] [-dpf Y|N (Y: post-filter on the device)]\n"
