@@ -101,6 +101,27 @@ __device__ unsigned long long gRowsProf[8];      // passes, passes that wrote re
 #ifndef YD_ROWS_M_LSHL_OR
 #define YD_ROWS_M_LSHL_OR YD_ROWS_SIGNSEL
 #endif
+// YD_ROWS_UNIFORM=1: the pass loop's wave-uniform state where the compiler keeps it on the scalar unit, and nothing copied for the loop's form.
+// (a) The loop has ONE exit: noMem is tested before the loop and together with `last` behind the pass's stores -- it can only be set at the top of a pass
+// (nextFlush); the refill and the results of that pass run as before and nothing the row code of that pass does is used after the loop, so every output is
+// as it was.  With two exits everything that lives across the loop (rows, cells, the chunk pointers, i, the query codes) had a second register and a v_mov or
+// two a pass.  (b) The uniform flags (noMem, insQ, insR, firstFill, exhausted) are unsigned words, not bool: a bool that lives across the loop is kept as a
+// lane mask or as a byte in a vector register (noMem: a v_and and v_readfirstlane at the head of every pass).  (c) The reference codes slide at the end
+// of the pass.  0: as before.  328 -> 308 vector instructions a common pass with YD_ROWS_ROWCOUNTS: profiles/ext_rows_pass_overhead.txt.
+#ifndef YD_ROWS_UNIFORM
+#define YD_ROWS_UNIFORM 1
+#endif
+#if YD_ROWS_UNIFORM
+typedef unsigned yd_uflag;
+#else
+typedef bool yd_uflag;
+#endif
+// YD_ROWS_ROWCOUNTS=1: the stream windows' per-lane counts come from the row number where they are needed -- every 8th pass -- instead of being counted down
+// in every pass: i entries of each stream are consumed after pass i, so buffered = qNext - 1 - i (rNext - 11 - i), and the reference has a base to give
+// while i < rLen - 10.  Three v_add and a v_mov fewer a pass.  0: qHave, rHave and rLeft carried and decremented.
+#ifndef YD_ROWS_ROWCOUNTS
+#define YD_ROWS_ROWCOUNTS 1
+#endif
 #ifndef YD_ROWS_WAVES
 #define YD_ROWS_WAVES 3                        // waves per SIMD of k_ext_rows_pk (a build switch for experiments: make variant VARIANT_FLAGS=-DYD_ROWS_WAVES=2)
 #endif
@@ -150,8 +171,9 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
     // buffered; after the pool's first fill (a partial dword + a full one) the buffered end is dword-aligned, so every refill is one full dword.  Nothing outside
     // the extension's own range is ever addressed (a dword is loaded only if it holds an entry of the range).
     uint32_t qwLo = 0, qwHi = 0, rwLo = 0, rwHi = 0, qLd = 0, rLd = 0, rOffP = 0, qPos = 0;
+    // (YD_ROWS_ROWCOUNTS: qHave / rHave are not carried -- qNext - 1 - i and rNext - 11 - i -- and rLeft holds rLen - 10, the first row without a base)
     int qHave = 0, rHave = 0, qNext = 0, rNext = 0, rLenP = 0, qStep = 0, rLeft = 0; bool pendQ = false, pendR = false, done = false;
-    bool insQ = false, insR = false;                                         // wave-uniform: the previous pass ran the query / reference refill
+    yd_uflag insQ = false, insR = false;                                         // wave-uniform: the previous pass ran the query / reference refill
     // the strand's PACKED codes (two to the byte, as the reference: k_pack4): entry idx of the extension = nibble qPos +- idx
     YD_GLOBAL const uint8_t *q4 = toGlobal(A.fwd4);
     unsigned calls = 0, rows = 0, cells = 0;
@@ -161,13 +183,13 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
 #pragma unroll
     for (int k = 0; k < YD_NP; k++) { PV[k] = LWg; PF[k] = LWp; rc[k] = 0x7FFF7FFFu; }      // (PV holds Vg = V - GOE throughout)
 
-    int poolCount = 0, poolNext = 0; bool exhausted = false;
+    int poolCount = 0, poolNext = 0; yd_uflag exhausted = false;
     // eMisc: flags | first query code << 8 | buffered entries (query | reference << 8) << 16
     uint32_t eLens = 0, eROff = 0, eQ = 0, eMisc = 0, eW1 = 0, eW2 = 0, ePidx = 0, eQwLo = 0, eQwHi = 0, eRwLo = 0, eRwHi = 0;
     // pendRes: the problem whose result this lane has yet to store (its state stays untouched until then); rowsFin: its last row
     bool pendFlush = false; int pendRes = -1, rowsFin = 0; unsigned pStart = 0;
     int wslot = 0; unsigned flush = 0; bool dirty = false, justDone = false;
-    YD_GLOBAL uint32_t *chunkPtr = toGlobal(A.trace); bool noMem = false;
+    YD_GLOBAL uint32_t *chunkPtr = toGlobal(A.trace); yd_uflag noMem = false;
     auto takeChunk = [&]() {                                                 // wave-uniform: the chunk of flushes [flush, flush + 16)
         unsigned c = 0;
         if (lane == 0) c = atomicAdd(A.chunkCount, 1u);
@@ -194,7 +216,7 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
         }
     };
     auto nextFlush = [&]() { flush++; if (flush % YD_CHUNK_FLUSHES == 0u) takeChunk(); };     // wave-uniform
-    bool firstFill = true;
+    yd_uflag firstFill = true;
 #if YD_ROWS_SIGNSEL
     uint32_t accA = 0, accB = 0, accAB2 = 0;                                 // the record's decision planes (bits 0 and 1 of accAB2's bytes are never written: they stay 0)
 #if YD_ROWS_SIGNSEL == 2
@@ -208,19 +230,27 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
 #define YD_ROWS_INS(k, s, acc) bfi(0x01010101u << (k), s, acc)
 #endif
 #endif
+#if YD_ROWS_UNIFORM
+    if (!YD_ROWS_EXIT(noMem))
+#endif
     for (;;) {
-        // (Round 6, measured and dropped: every wave-uniform condition of this loop through UNI_B and every uniform counter through uni().  Left to itself the compiler
-        // takes the loop's exits for lane-dependent -- an EXEC-masked loop, the uniform state in vector registers, twenty moves and thirty mask instructions a pass --
-        // but the scalar version waits for a v_readfirstlane before every branch: 14.42 -> 15.84 ms a launch, profiles/r06_rows_kernel_passes.txt.)
+        // (Round 6, measured and dropped: every wave-uniform condition of this loop through UNI_B and every uniform counter through uni(): the scalar version waits
+        // for a v_readfirstlane before every branch, 14.42 -> 15.84 ms a launch, profiles/r06_rows_kernel_passes.txt.  What the compiled loop really held in vector
+        // registers was less than that note took it for -- its branches, wslot and flush were scalar; noMem, insQ and the copies for its second exit were not: see
+        // YD_ROWS_UNIFORM and profiles/ext_rows_pass_overhead.txt.)
+#if !YD_ROWS_UNIFORM
         if (YD_ROWS_EXIT(noMem)) break;
+#endif
         // What the previous iteration loaded is consumed HERE, before this iteration issues any store (the memory counter is in-order: a wait for these loads
         // further down would also wait for the stores issued in between).  Slide the reference window: pair k takes pair k+1; pair 10's low half takes what
         // was pair 1's high half, its high half the new base.  (A lane that starts a problem below overwrites the window.)
+#if !YD_ROWS_UNIFORM
         {
 #pragma unroll
             for (int k = 0; k + 1 < YD_NP; k++) rc[k] = rc[k + 1];
             rc[YD_NP - 1] = (rc[0] >> 16) | ((nbNext | YD_RCREAL) << 16);
         }
+#endif
         // the dwords the previous pass loaded go to the ends of the windows (entries in consumption order: a reverse extension's bytes, and its nibbles, swapped)
         if (insQ) {
             if (pendQ) {
@@ -230,6 +260,9 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
 #endif
                 const uint32_t sw = ((qLd & 0x0F0F0F0Fu) << 4) | ((qLd >> 4) & 0x0F0F0F0Fu);      // forward: the even offset (high nibble) first
                 const uint32_t v = qStep < 0 ? __builtin_amdgcn_perm(0u, qLd, 0x00010203u) : sw;   // reverse: bytes swapped, each byte's low nibble (the higher offset) first
+#if YD_ROWS_ROWCOUNTS
+                qHave = qNext - 1 - i;
+#endif
                 const unsigned long long t = (unsigned long long)v << (4 * (qHave & 15));
                 qwLo |= (uint32_t)t; qwHi |= (uint32_t)(t >> 32); qHave += 8; qNext += 8;
             }
@@ -242,6 +275,9 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
 #endif
                 const uint32_t sw = ((rLd & 0x0F0F0F0Fu) << 4) | ((rLd >> 4) & 0x0F0F0F0Fu);      // forward: the even offset (high nibble) first
                 const uint32_t v = qStep < 0 ? __builtin_amdgcn_perm(0u, rLd, 0x00010203u) : sw;   // reverse: bytes swapped, each byte's low nibble (the higher offset) first
+#if YD_ROWS_ROWCOUNTS
+                rHave = rNext - 11 - i;
+#endif
                 const unsigned long long t = (unsigned long long)v << (4 * (rHave & 15));
                 rwLo |= (uint32_t)t; rwHi |= (uint32_t)(t >> 32); rHave += 8; rNext += 8;
             }
@@ -250,8 +286,8 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
         // the blocks the previous iteration completed: their place is fixed now (a problem that starts below notes the flush ITS first block will go out
         // with), the stores themselves are issued after this iteration's loads (program order = the order the memory counter retires in)
         unsigned long long flushNow = 0ull; YD_GLOBAL uint32_t *flushSlot = chunkPtr;
-        if (wslot == 0) { flushNow = __ballot(pendFlush); pendFlush = false; if (flushNow != 0ull) { flushSlot = chunkPtr + (size_t)(flush % YD_CHUNK_FLUSHES) * 32u; nextFlush();
-            } }
+        if (wslot == 0) { flushNow = __ballot(pendFlush); pendFlush = false;
+            if (flushNow != 0ull) { flushSlot = chunkPtr + (size_t)(flush % YD_CHUNK_FLUSHES) * 32u; nextFlush(); } }
         // ---- refill (k_ext_rows') ----
         for (;;) {
             const unsigned long long need = __ballot(p < 0 && !done && !justDone && (!YD_ROWS_RESBATCH || pendRes < 0));
@@ -377,10 +413,18 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
         ++i;
         const int qc = qcNext;
         // next iteration's query code (index i) and the reference nibble that enters the window (index i + 10; 15 beyond the reference): off the windows' low ends
+#if YD_ROWS_ROWCOUNTS
+        qcNext = (int)(qwLo & 15u); qwLo = __builtin_amdgcn_alignbit(qwHi, qwLo, 4); qwHi >>= 4;
+        { nbNext = i < rLeft ? (rwLo & 15u) : 15u; rwLo = __builtin_amdgcn_alignbit(rwHi, rwLo, 4); rwHi >>= 4; }
+#else
         qcNext = (int)(qwLo & 15u); qwLo = __builtin_amdgcn_alignbit(qwHi, qwLo, 4); qwHi >>= 4; qHave--;
         { rLeft--; nbNext = rLeft > 0 ? (rwLo & 15u) : 15u; rwLo = __builtin_amdgcn_alignbit(rwHi, rwLo, 4); rwHi >>= 4; rHave--; }
+#endif
         // refills (wave-uniform schedule): the loads are consumed at the top of the next pass
         if (wslot == 0) {
+#if YD_ROWS_ROWCOUNTS
+            qHave = qNext - 1 - i; rHave = rNext - 11 - i;
+#endif
             pendQ = qHave <= 8 && qNext < qLen;
 #if YD_ROWS_LDSWIN
             // the dword that is due: out of the lane's staged piece -- or, when it is the first dword of the next aligned 16-byte piece (the last one going down), or the
@@ -440,7 +484,7 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
                 YD_GLOBAL yd_u32x4 *dst = (YD_GLOBAL yd_u32x4 *)toGlobal(&A.res[pendRes]); YD_STORE_NT(dst, lo); YD_STORE_NT(dst + 1, hi); } pendRes = -1;
         }
         flushBlocks(flushNow, flushSlot);
-        if (YD_ROWS_EXIT(last)) break;
+        if (YD_ROWS_EXIT(last || (YD_ROWS_UNIFORM && noMem))) break;      // (noMem: set at the top of this pass at the earliest; see YD_ROWS_UNIFORM)
         const uint32_t qcP = ((uint32_t)qc | ((uint32_t)qcPrev << 16)) ^ (YD_RCREAL * 0x10001u);      // code ^ qcP = nibble ^ query code
         qcPrev = qc;
         uint32_t qcPv = qcP; asm volatile("" : "+v"(qcPv));                   // (opaque: else the constant is re-applied in every pair)
@@ -522,11 +566,21 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(YD_ROWS
         if (busy) dirty = true;
         if (wslot == 7) { pendFlush = dirty; dirty = false; wslot = 0; } else wslot++;      // wave-uniform
         justDone = fin;                                                      // the next record slot stays empty behind a finished problem (its traceback's spare record)
-        // A finished lane keeps its state: the result is stored from it in the next pass; its byte streams stay inside the finished extension (clamped index,
-        // rLeft <= 0), so an idle lane's loads are harmless.
+        // A finished lane keeps its state: the result is stored from it in the next pass; its streams stay inside the finished extension (a refill loads only
+        // while qNext < qLen / rNext < rLen, and behind the reference's end -- rLeft <= 0, or i >= rLeft with YD_ROWS_ROWCOUNTS -- the base is 15), so an idle
+        // lane's loads are harmless.
         if (fin) { pendRes = p; p = -1; rowsFin = row; }
 #ifdef YD_PROF
         if (__ballot(snap) != 0ull) pfSnap++; pfBusy += (unsigned)__builtin_popcountll(__ballot(busy));
+#endif
+#if YD_ROWS_UNIFORM
+        // the slide of the reference window (see the loop's head), at the END of the pass: the same values in the same order -- before the next pass's refill can
+        // start a problem in the lane -- but one set of moves; at the head the compiler slid the window into a second set of registers and copied it back
+        {
+#pragma unroll
+            for (int k = 0; k + 1 < YD_NP; k++) rc[k] = rc[k + 1];
+            rc[YD_NP - 1] = (rc[0] >> 16) | ((nbNext | YD_RCREAL) << 16);
+        }
 #endif
     }
     if (wslot != 0 && dirty) pendFlush = true;
